@@ -22,7 +22,11 @@ SURVEY 8d), the same set at C2 under "c2", and `cpu_baseline` -- the oracle
 timed on this host in a child process that never touches the GPU (single-core
 grid MVMs/sec; NLL+gradient with multiprocessing.Pool(cpu_count()) over the N+1
 solves as reference benchmarks/benchlib/bench.py:214-227 does).
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  Every timed loop runs exactly --steps steps after
+--warmup untimed ones.  --dump-outputs DIR writes what the headline product and
+the NLL+gradient step returned in their last step as DIR/<name>.npy (float64,
+64 MB at most; inputs are seeded, so two builds can be compared output for
+output).
 """
 import argparse
 import json
@@ -40,6 +44,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 TRAFFIC_FILE = os.path.join(ROOT, 'profiles', 'r06', 'traffic.json')
+DUMP_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_PRODUCT_BYTES = 48 << 20   # ... of which the headline product's sample
 
 
 def parse():
@@ -69,6 +75,11 @@ def parse():
                     help='iteration cap of that step (the C5 residuals stop falling there)')
     ap.add_argument('--cpu-seconds', type=float, default=8.0,
                     help='budget of each bounded CPU sample')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the timed paths returned in their last step as DIR/<name>.npy '
+                         '(rank 0; a fixed, seeded column sample of the headline product, %d MB at '
+                         'most in all) so that two builds can be compared output for output'
+                         % (DUMP_BYTES >> 20))
     # debugging aids for the multi-rank path on a one-GPU box
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'])
     ap.add_argument('--force-dist', action='store_true',
@@ -83,7 +94,10 @@ def parse():
                          'cpu_full_length_c5.txt)')
     # internal: the CPU-baseline child process (never imports torch)
     ap.add_argument('--cpu-child', default=None, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 # ---------------------------------------------------------------------------
@@ -418,6 +432,28 @@ def measured_traffic(config, batch, form='fft'):
     return (e['bytes_per_step'], e['source']) if e else (None, None)
 
 
+def product_sample(Y, nbytes=DUMP_PRODUCT_BYTES):
+    """(sample, columns) of a device batch Y for --dump-outputs: every row of Y at a fixed, seeded,
+    sorted set of columns that fits in `nbytes` (all columns when Y fits), copied to the host."""
+    import torch
+    rows, cols = Y.shape
+    keep = max(1, min(cols, nbytes // (Y.element_size() * rows)))
+    idx = np.arange(cols) if keep == cols else \
+        np.sort(np.random.RandomState(0).choice(cols, keep, replace=False))
+    return Y.index_select(1, torch.from_numpy(idx).to(Y.device)).cpu().numpy(), idx
+
+
+def write_dumps(path, arrays):
+    """--dump-outputs: one float64 .npy per array under `path`."""
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, 'dumped outputs of %d bytes exceed %d' % (total, DUMP_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def flat_gradient(g):
     """The four gradient families of a step as one vector (coreg vectors, coreg
     diagonals, kernel parameters, noise)."""
@@ -550,13 +586,15 @@ def gpu_nll_grad(p, probes_local, n_probes_global, group=None, repeats=2, scipy_
         if k_ in info and not np.isfinite(info[k_]):
             info[k_] = None                       # (strict JSON has no NaN)
     if keep_gradient:
-        info['_gradient'] = flat_gradient(g)      # (popped by the caller: not part of the line)
+        # the last pass's results (popped by the caller: not part of the line)
+        info['_gradient'] = flat_gradient(g)
+        info['_nll_logdet'] = np.array([-ll, logdet], dtype=np.float64)
     info['seconds'] = best
     info['seconds_per_iteration'] = best / max(info['iterations_max'], 1)
     return info
 
 
-def time_full_operator(g, p, batch, gen, steps, world, dev, alg):
+def time_full_operator(g, p, batch, gen, steps, warmup, world, dev, alg):
     """K~ = W K_UU W^T + eps on `batch` data-space vectors."""
     import torch
     from runlmc_amd._native import SkiOp
@@ -564,13 +602,12 @@ def time_full_operator(g, p, batch, gen, steps, world, dev, alg):
     s.set_noise(p.noise, p.lens)
     Xd = torch.randn(batch, p.n, dtype=torch.float64, generator=gen).to(dev)
     Yd = torch.empty_like(Xd)
-    fsteps = max(3, steps // 2)
-    fwall, fev = time_steps(lambda: s.mvm(Xd, out=Yd), fsteps, 2, world, dev)
+    fwall, fev = time_steps(lambda: s.mvm(Xd, out=Yd), steps, warmup, world, dev)
     fwall = max_over_ranks(fwall, world, dev)
     nnz = int(p.W.nnz)
     full_alg = alg + 8 * 3 * p.n * batch + 2 * (nnz * 12 + (p.n + 1) * 4)
     return {'mvm_per_s': batch * world / (fwall * 1e-3), 'ms_per_step': fwall,
-            'steps': fsteps, 'n': p.n,
+            'steps': steps, 'n': p.n,
             'roofline_frac': full_alg / (fwall * 1e-3) / 1e9 / HBM_PEAK_GBS,
             'algorithmic_bytes_per_step': full_alg,
             'what': 'K~ x = W (K_UU (W^T x)) + eps * x on %d data-space vectors in the CALLER\'s row '
@@ -676,6 +713,10 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
     X = torch.randn(batch, D * p.m, dtype=torch.float64, generator=gen).to(dev)
     Y = torch.empty_like(X)
     wall_ms, ev_ms = time_steps(lambda: g.mvm(X, out=Y), steps, warmup, world, dev)
+    # (before anything below reuses Y: the product of the last timed step)
+    dump = {} if headline and args.dump_outputs and rank == 0 else None
+    if dump is not None:
+        dump['grid_mvm'], dump['grid_mvm_columns'] = product_sample(Y)
     wall_ms = max_over_ranks(wall_ms, world, dev)
     ev_ms = max_over_ranks(ev_ms, world, dev)
     mvms = batch * world / (wall_ms * 1e-3)
@@ -713,7 +754,7 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
         # kernel: read X once, write Y once -- the algorithmic traffic of the product), same
         # clock: the interface's 8 TB/s is `peak`, this is what a read-once / write-once
         # kernel pair can be held against (tools/lr_pattern_probe.hip)
-        c_ms, _ = time_steps(lambda: torch.mul(X, 1.0, out=Y), 20, 5, world, dev)
+        c_ms, _ = time_steps(lambda: torch.mul(X, 1.0, out=Y), steps, warmup, world, dev)
         c_ms = max_over_ranks(c_ms, world, dev)
         copy_gbs = 2.0 * X.numel() * 8 / (c_ms * 1e-3) / 1e9
         out['roofline']['copy_same_vectors'] = {
@@ -746,7 +787,7 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
         out['families'] = fam
 
     if not args.no_full:
-        out['full_mvm'] = time_full_operator(g, p, batch, gen, steps, world, dev, alg)
+        out['full_mvm'] = time_full_operator(g, p, batch, gen, steps, warmup, world, dev, alg)
 
     if not args.no_sweep and world == 1:
         # the N+1-vector batch is what a solver round carries; larger batches
@@ -757,7 +798,7 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
                 continue
             Xb = torch.randn(b, D * p.m, dtype=torch.float64, device=dev)
             Yb = torch.empty_like(Xb)
-            w_ms, _ = time_steps(lambda: g.mvm(Xb, out=Yb), max(3, steps // 4), 2, 1, dev)
+            w_ms, _ = time_steps(lambda: g.mvm(Xb, out=Yb), steps, warmup, 1, dev)
             ab = synth.algorithmic_bytes_grid_mvm(D, Q, p.m, g.L, b)
             sweep[str(b)] = {'mvm_per_s': b / (w_ms * 1e-3),
                              'roofline_frac': ab / (w_ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
@@ -785,6 +826,9 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
             # 1e-4 rule; log det exact), Krylov solves otherwise (matern, mix)
             info = gpu_nll_grad(pe, probes, n_probes, group=group, keep_gradient=True)
             grad_default = info.pop('_gradient')
+            nll_logdet = info.pop('_nll_logdet')
+            if key == 'nll_grad' and dump is not None:
+                dump.update(nll_grad_gradient=grad_default, nll_grad_nll_logdet=nll_logdet)
             info['seconds'] = max_over_ranks(info['seconds'], world, dev)
             info.update(n_probes_global=n_probes, scaling='strong', eps=eps,
                         probes_per_rank=-(-n_probes // world),
@@ -832,6 +876,7 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
             kry = gpu_nll_grad(pe, probes, n_probes, group=group, keep_gradient=True,
                                precondition=False)
             grad_kry = kry.pop('_gradient')
+            kry.pop('_nll_logdet')
             kry['seconds'] = max_over_ranks(kry['seconds'], world, dev)
             if world > 1:
                 # the probe-parallel axis proper (reference lmc/stochastic_deriv.py:39-52): the
@@ -870,6 +915,7 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
                                   scipy_exits=False, maxiter=args.stall_iters,
                                   keep_gradient=True, precondition=False)
                 grad_stall = st.pop('_gradient')
+                st.pop('_nll_logdet')
                 st.update(n_probes_global=n_probes, eps=eps, maxiter=args.stall_iters,
                           stopping='reference residual rule only (RL_MINRES_RULE), capped at '
                                    'the stall of the fp64 residuals',
@@ -887,6 +933,8 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
                                 precondition=False)
             info.update(n_probes_global=n_probes, eps=0.1, stopping='reference residual rule only')
             out['nll_grad_krylov_to_tolerance'] = info
+    if dump is not None:
+        out['_dump'] = dump
     return out
 
 
@@ -939,6 +987,7 @@ def main():
     dev = torch.device('cuda', torch.cuda.current_device())
 
     head = bench_config(args.config, args, rank, world, dev, args.steps, args.warmup, True)
+    dump = head.pop('_dump', None)
     out = {
         'metric': 'kronecker_toeplitz_mvms_per_sec',
         'value': head.pop('value'), 'unit': 'MVM/s', 'n_gpus': world, 'steps': args.steps,
@@ -951,8 +1000,7 @@ def main():
     if other and not args.no_extra and world == 1:
         # the small synthetic configuration of BASELINE.json as an extra key
         # (17 vectors per step: launch-latency-bound by construction)
-        out[other] = bench_config(other, args, rank, world, dev, max(args.steps, 100),
-                                  max(args.warmup, 10), False)
+        out[other] = bench_config(other, args, rank, world, dev, args.steps, args.warmup, False)
 
     if rank == 0 and world == 1 and not args.no_cpu:
         jobs = {args.config: dict(config=args.config, mvm=True, kern=args.kern)}
@@ -1022,6 +1070,8 @@ def main():
                               'forced_in_world_of_one': bool(args.force_dist and world == 1),
                               'per_step': 'broadcast of alpha (n doubles) + one all-reduce of '
                                           'the gradient partials'}
+    if dump is not None:
+        out['dump_outputs'] = write_dumps(args.dump_outputs, dump)
     if rank == 0:
         print(json.dumps(out))
     if world > 1 or args.force_dist:
