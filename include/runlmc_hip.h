@@ -31,18 +31,21 @@ extern "C" {
 #define RL_EHIP 2     /* HIP runtime error */
 #define RL_ENOMEM 3
 #define RL_ELIMIT 4   /* problem exceeds a documented kernel limit */
+#define RL_ENOTPD 5   /* a Cholesky factorisation met a pivot that is not a positive finite number */
 
 typedef struct rl_gridop rl_gridop;
 typedef struct rl_ski rl_ski;
+typedef struct rl_exact rl_exact;
 
 /* Version of this ABI: bumped whenever a declared signature changes (2: rl_solve_batch_lanczos
  * gained `method`, round 4; 3: rl_gridop_form_stats added, round 5; 4: rl_ski_factor,
  * rl_solve_direct, rl_solve_pcg, rl_ski_project,
  * rl_gridop_project, rl_gridop_set_rank_hint, rl_gridop_poly_coeffs, rl_slq_log_quadrature,
- * rl_probes_to_int8 added, round 6; callers built against an older version must be rebuilt).  A binding
+ * rl_probes_to_int8 added, round 6; 5: the rl_exact_* handle of the exact likelihood; callers
+ * built against an older version must be rebuilt).  A binding
  * compares rl_abi_version() with the RL_ABI_VERSION it was written against before its
  * first call (runlmc_amd/_lib.py does) instead of finding out through shifted arguments. */
-#define RL_ABI_VERSION 4
+#define RL_ABI_VERSION 5
 int rl_abi_version(void);
 
 const char* rl_last_error(void);
@@ -362,6 +365,60 @@ int rl_cross_dots(const double* U, const double* V, int nvec, int D, int m, doub
  * offsets dev int[D+1], U, V dev [nvec][n], out dev [nvec][D].                */
 int rl_segment_dots(const double* U, const double* V, const int* offsets, int nvec, int n,
                     int D, double* out, void* stream);
+
+/* ---- exact (dense) LMC likelihood ------------------------------------------
+ * Replaces ExactLMCLikelihood (runlmc/lmc/likelihood.py:137-217: the dense K, scipy's
+ * cho_factor, ExactDeriv's alpha and K^-1, exact_deriv.py:13-23) and the dense pieces the model
+ * takes from it (models/interpolated_llgp.py:248-260 K(), 262-276 log det, 350-356 'exact'
+ * variances).  fp64 throughout; ONE n x n device buffer (K, then L, then the lower triangle of
+ * K^-1) plus O(64 n) workspaces, so n is bounded by free device memory (RL_ENOMEM past it).
+ *   K = sum_q B_q[d(i), d(j)] k_q(r_q(x_i, x_j)) + diag(noise[d(i)]),  r_q the Euclidean distance
+ *   over kernel q's active input columns, rows = outputs concatenated (likelihood.py:30-31).
+ * Limits (RL_ELIMIT): D <= 64, Q + sum_q p_q <= 32 (p_q: parameters of kernel q), <= 4 active
+ * columns per kernel.  Synchronous except rl_exact_solve.                                        */
+#define RL_EXACT_RBF 0          /* exp(-g r^2 / 2)              params [g]        (kern/rbf.py) */
+#define RL_EXACT_MATERN32 1     /* (1 + s) e^-s, s = sqrt(3) g r  params [g]      (kern/matern32.py) */
+#define RL_EXACT_STDPERIODIC 2  /* exp(-g sin^2(pi r / T) / 2)  params [g, T]     (kern/std_periodic.py) */
+#define RL_EXACT_SCALED 16      /* OR'ed in: c k(r), params[2] = c, one more parameter (kern/scaled.py) */
+/* n data points of P input columns each. */
+int rl_exact_create(int device, int n, int P, rl_exact** out);
+int rl_exact_destroy(rl_exact* h);
+/* Parameters (per optimiser step; nothing is computed yet):
+ *   X host [n][P]; lens host [D] (sum n); kinds host [Q]; params host [Q][4];
+ *   active_cols host [Q][4] (column indices, -1 after the last); B host [Q][D][D]; noise host [D].
+ * The parameters of kernel q are ordered as its kernel_gradient (derivatives), which fixes the
+ * slots of rl_exact_grad_sums.                                                                  */
+int rl_exact_set(rl_exact* h, const double* X, const int* lens, int D, int Q, const int* kinds,
+                 const double* params, const int* active_cols, const double* B, const double* noise);
+/* K into the device buffer (lower triangle; rl_exact_factor does it when needed). */
+int rl_exact_assemble(rl_exact* h);
+/* Blocked Cholesky K = L L^T in place (cho_factor, likelihood.py:153) and
+ * *logdet = 2 sum log L_ii (models/interpolated_llgp.py:262-276), summed in a fixed order.  A pivot
+ * that is not a positive finite number returns RL_ENOTPD with *bad_col = its column (else -1);
+ * the handle keeps its parameters and can be set and factored again.                           */
+int rl_exact_factor(rl_exact* h, double* logdet, int* bad_col);
+/* X[v] = K^-1 B[v] (cho_solve, exact_deriv.py:18-19), B, X dev [nrhs][n] (may alias).        */
+int rl_exact_solve(rl_exact* h, const double* B, double* X, int nrhs, void* stream);
+/* out[t] = || L^-1 K(X, x_t) ||^2 = diag(K_*X K^-1 K_X*) for test rows Xtest host [nt][P] of
+ * outputs test_lens [D] (interpolated_llgp.py:350-356); out host [nt].  Needs the factor.      */
+int rl_exact_explained_variance(rl_exact* h, const double* Xtest, const int* test_lens, double* out);
+/* The noise-free cross-covariance K(Xtest, X), out host [nt][n]
+ * (ExactLMCLikelihood.kernel_from_indices, likelihood.py:176-199).  Needs only rl_exact_set.    */
+int rl_exact_cross_host(rl_exact* h, const double* Xtest, const int* test_lens, double* out);
+/* The whole K, out host [n][n] (likelihood.py:149-151; interpolated_llgp.py:248-260).  Built
+ * anew in row panels: valid in any state after rl_exact_set, O(n^2) host memory.               */
+int rl_exact_dense_host(rl_exact* h, double* out);
+/* K^-1 (lower) in place of the factor: L^-1 (blocked trtri), then L^-T L^-1 (blocked lauum).
+ * Afterwards rl_exact_solve / rl_exact_explained_variance need rl_exact_factor again.          */
+int rl_exact_invert(rl_exact* h);
+/* Gradient block sums of the exact likelihood (the loops of likelihood.py:48-96 over
+ * exact_deriv.py:13-23), with M = alpha alpha^T - K^-1 (never formed):
+ *   out[s][a][b] = sum_{i in a, j in b} M_ij v_s(i, j)   for s < S = Q + sum_q p_q:
+ *                  v_q = k_q (s = q), then dk_q / dtheta_p (s = Q + sum_{q' < q} p_q' + p);
+ *   out[S D^2 + d] = sum_{i in d} M_ii.
+ * alpha dev [n] (= K^-1 y); out host [S D^2 + D].  Inverts first if needed.  Bit-identical from
+ * call to call (fixed reduction order).  dL/dtheta = 1/2 sum_ab dB[a, b] out[s][a][b].           */
+int rl_exact_grad_sums(rl_exact* h, const double* alpha, double* out);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB = os.path.join(HERE, 'csrc', 'librunlmc_hip.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'runlmc_hip.h')
 
-RL_OK, RL_EINVAL, RL_EHIP, RL_ENOMEM, RL_ELIMIT = 0, 1, 2, 3, 4
+RL_OK, RL_EINVAL, RL_EHIP, RL_ENOMEM, RL_ELIMIT, RL_ENOTPD = 0, 1, 2, 3, 4, 5
 
 _c_int_p = ctypes.POINTER(ctypes.c_int)
 _c_dbl_p = ctypes.POINTER(ctypes.c_double)
@@ -66,8 +66,19 @@ _SIGNATURES = {
     'rl_ski_precond_sample': [_vp, _vp, _vp, _i, _c_dbl_p, _vp],
     'rl_cross_dots': [_vp, _vp, _i, _i, _i, _vp, _vp],
     'rl_segment_dots': [_vp, _vp, _vp, _i, _i, _i, _vp, _vp],
+    'rl_exact_create': [_i, _i, _i, ctypes.POINTER(_vp)],
+    'rl_exact_destroy': [_vp],
+    'rl_exact_set': [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    'rl_exact_assemble': [_vp],
+    'rl_exact_factor': [_vp, _c_dbl_p, _c_int_p],
+    'rl_exact_solve': [_vp, _vp, _vp, _i, _vp],
+    'rl_exact_explained_variance': [_vp, _vp, _vp, _vp],
+    'rl_exact_cross_host': [_vp, _vp, _vp, _vp],
+    'rl_exact_dense_host': [_vp, _vp],
+    'rl_exact_invert': [_vp],
+    'rl_exact_grad_sums': [_vp, _vp, _vp],
 }
-ABI_VERSION = 4      # include/runlmc_hip.h: RL_ABI_VERSION
+ABI_VERSION = 5      # include/runlmc_hip.h: RL_ABI_VERSION
 _RESTYPE = {'rl_last_error': ctypes.c_char_p, 'rl_backend': ctypes.c_char_p}
 
 
@@ -124,6 +135,8 @@ class NativeLib:
             raise NotImplementedError(msg)
         if rc == RL_ENOMEM:
             raise MemoryError(msg)
+        if rc == RL_ENOTPD:
+            raise np.linalg.LinAlgError(msg)
         raise NativeError(msg)
 
     def call(self, name, *args):

@@ -488,3 +488,150 @@ def segment_dots(lib, U, V, offsets_dev, D):
     lib.call('rl_segment_dots', dev_ptr(U), dev_ptr(V), dev_ptr(offsets_dev),
              k, int(n), int(D), dev_ptr(out), lib.stream_ptr(U.device))
     return out
+
+
+# ---- exact (dense) likelihood: include/runlmc_hip.h rl_exact_* ----------------------------------
+RL_EXACT_SCALED = 16
+EXACT_MAX_COLS = 4
+
+
+def exact_descriptors(kernels):
+    """(kinds [Q], params [Q, 4], active columns [Q, 4], parameters per kernel) of the package's
+    kernels for rl_exact_set.  A kernel class without a device formula raises
+    NotImplementedError naming it: there is no host fallback."""
+    from .kern.stationary import RBF, Matern32, StdPeriodic, Scaled
+    base = {RBF: 0, Matern32: 1, StdPeriodic: 2}
+    kinds, params, cols, nder = [], [], [], []
+    for k in kernels:
+        scaled = type(k) is Scaled
+        inner = k.k if scaled else k
+        if type(inner) not in base:
+            raise NotImplementedError(
+                'the exact likelihood has no device kernel for %s' % type(inner if scaled else k).__name__)
+        kind = base[type(inner)] | (RL_EXACT_SCALED if scaled else 0)
+        period = inner.period if type(inner) is StdPeriodic else 0.0
+        params.append([inner.inv_lengthscale, period, k.scale if scaled else 0.0, 0.0])
+        ad = list(k.active_dims)
+        if not ad:
+            raise ValueError('kernel %s has no active dimensions' % k.name)
+        if len(ad) > EXACT_MAX_COLS:
+            raise NotImplementedError('the exact likelihood takes kernels on at most %d input '
+                                      'dimensions, %s has %d' % (EXACT_MAX_COLS, k.name, len(ad)))
+        cols.append(ad + [-1] * (EXACT_MAX_COLS - len(ad)))
+        kinds.append(kind)
+        nder.append((2 if kind & 15 == 2 else 1) + (1 if scaled else 0))
+    return (np.array(kinds, dtype=np.int32), np.array(params, dtype=np.float64),
+            np.array(cols, dtype=np.int32), nder)
+
+
+class ExactOp:
+    """Device handle of the dense exact LMC covariance, its Cholesky factor and K^-1
+    (include/runlmc_hip.h: rl_exact_*)."""
+
+    def __init__(self, n, P, device_index=0, lib=None):
+        self.lib = lib or _lib.get_library()
+        self.n, self.P = int(n), int(P)
+        self.device = self.lib.torch_device(device_index)
+        self._h = ctypes.c_void_p()
+        self.lib.call('rl_exact_create', device_index, self.n, self.P, ctypes.byref(self._h))
+        self.D = self.Q = None
+        self.nder = []
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h is not None and h.value:
+            self.lib.cdll.rl_exact_destroy(h)
+            self._h = ctypes.c_void_p()
+
+    def _rows(self, X, lens, what):
+        lens = np.ascontiguousarray(np.asarray(lens), dtype=np.int32)
+        if self.D is not None and lens.shape != (self.D,):
+            raise ValueError('%s: expected %d output lengths, got shape %s'
+                             % (what, self.D, lens.shape))
+        X = as_f64(X)
+        if X.ndim == 1 and self.P == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2 or X.shape != (int(lens.sum()), self.P):
+            raise ValueError('%s: expected inputs of shape (%d, %d), got %s'
+                             % (what, int(lens.sum()), self.P, X.shape))
+        return np.ascontiguousarray(X), lens
+
+    def set(self, X, lens, kernels, coreg_mats, noise):
+        """Data X (n, P) with rows the outputs concatenated, `lens` per output, the kernels
+        (runlmc_amd.kern), B_q (Q, D, D) and the noise (D,) -- rl_exact_set."""
+        kinds, params, cols, nder = exact_descriptors(kernels)
+        B = as_f64(np.asarray(coreg_mats, dtype=np.float64))
+        D = int(np.size(lens))
+        if B.shape != (len(kinds), D, D):
+            raise ValueError('expected %d coregionalisation matrices of %d x %d, got %s'
+                             % (len(kinds), D, D, B.shape))
+        noise = as_f64(noise).reshape(-1)
+        if noise.shape != (D,):
+            raise ValueError('expected %d noise values, got %d' % (D, noise.size))
+        self.D = None
+        X, lens = self._rows(X, lens, 'rl_exact_set')
+        if X.shape[0] != self.n:
+            raise ValueError('the handle holds %d points, got %d' % (self.n, X.shape[0]))
+        self.lib.call('rl_exact_set', self._h, host_ptr(X), host_ptr(lens), D, len(kinds),
+                      host_ptr(kinds), host_ptr(params), host_ptr(cols), host_ptr(B), host_ptr(noise))
+        self.D, self.Q, self.nder = D, len(kinds), nder
+
+    def assemble(self):
+        self.lib.call('rl_exact_assemble', self._h)
+
+    def factor(self):
+        """log det K; numpy.linalg.LinAlgError naming the column of a bad pivot (as
+        scipy.linalg.cho_factor does)."""
+        ld, bad = ctypes.c_double(), ctypes.c_int(-1)
+        rc = self.lib.cdll.rl_exact_factor(self._h, ctypes.byref(ld), ctypes.byref(bad))
+        if rc == _lib.RL_ENOTPD:
+            raise np.linalg.LinAlgError(
+                '%d-th leading minor of the array is not positive definite (column %d)'
+                % (bad.value + 1, bad.value))
+        self.lib.check(rc)
+        return ld.value
+
+    def solve(self, B):
+        """K^-1 B[v] for the rows of B ((k, n) or (n,), numpy or device tensor); a device tensor."""
+        t, single = _vec_batch(self.lib, B, self.n, self.device)
+        out = torch.empty_like(t)
+        self.lib.call('rl_exact_solve', self._h, dev_ptr(t), dev_ptr(out), t.shape[0],
+                      self.lib.stream_ptr(self.device))
+        return out[0] if single else out
+
+    def explained_variance(self, Xt, test_lens):
+        """diag(K_*X K^-1 K_X*) for test rows Xt (nt, P) of outputs test_lens."""
+        Xt, tl = self._rows(Xt, test_lens, 'explained_variance')
+        out = np.zeros(Xt.shape[0])
+        self.lib.call('rl_exact_explained_variance', self._h, host_ptr(Xt), host_ptr(tl),
+                      host_ptr(out))
+        return out
+
+    def cross(self, Xt, test_lens):
+        """Noise-free K(Xt, X), (nt, n)."""
+        Xt, tl = self._rows(Xt, test_lens, 'cross')
+        out = np.zeros((Xt.shape[0], self.n))
+        self.lib.call('rl_exact_cross_host', self._h, host_ptr(Xt), host_ptr(tl), host_ptr(out))
+        return out
+
+    def dense(self):
+        """The whole K, (n, n) on the host."""
+        out = np.zeros((self.n, self.n))
+        self.lib.call('rl_exact_dense_host', self._h, host_ptr(out))
+        return out
+
+    def invert(self):
+        self.lib.call('rl_exact_invert', self._h)
+
+    def grad_sums(self, alpha):
+        """(S, noise_sums): S[s] = sum over output blocks of M * v_s, M = alpha alpha^T - K^-1,
+        v_s = k_q (s = q < Q) then dk_q / dtheta_p in order; noise_sums[d] = sum_{i in d} M_ii
+        (rl_exact_grad_sums)."""
+        a = alpha if isinstance(alpha, torch.Tensor) else torch.from_numpy(as_f64(alpha))
+        a = a.to(self.device, torch.float64).contiguous()
+        if a.shape != (self.n,):
+            raise ValueError('alpha must have %d entries' % self.n)
+        ns, D = self.Q + sum(self.nder), self.D
+        out = np.zeros(ns * D * D + D)
+        self.lib.call('rl_exact_grad_sums', self._h, dev_ptr(a), host_ptr(out))
+        return out[:ns * D * D].reshape(ns, D, D), out[ns * D * D:].copy()

@@ -15,9 +15,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
-# three translation units (rl_host.h holds what they share); runlmc_hip.hip includes all three
+# four translation units (rl_host.h holds what they share); runlmc_hip.hip includes all of them
 # (experiment builds that need one code object)
-SOURCES = [os.path.join(CSRC, n) for n in ('rl_gridop.hip', 'rl_ski.hip', 'rl_solve.hip')]
+SOURCES = [os.path.join(CSRC, n) for n in ('rl_gridop.hip', 'rl_ski.hip', 'rl_solve.hip',
+                                            'rl_exact.hip')]
 UNITY = os.path.join(CSRC, 'runlmc_hip.hip')
 import glob
 HEADERS = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + [
@@ -67,7 +68,7 @@ def build_hip(force=False, extra=(), unity=False, out=None):
     os.makedirs(OBJ_DIR, exist_ok=True)
     objs = [os.path.join(OBJ_DIR, os.path.basename(s)[:-4] + '.hip.o') for s in SOURCES]
     # (per object: a file whose source and headers are older than its object is not recompiled --
-    # an edit of the solver costs one translation unit, not three)
+    # an edit of the solver costs one translation unit, not four)
     todo = [(s, o) for s, o in zip(SOURCES, objs)
             if force or extra or _stale(o, [s] + HEADERS + [__file__])]
     if todo:

@@ -1,0 +1,520 @@
+// Dense fp64 kernels of the exact LMC likelihood (rl_exact.hip) and the blocked Cholesky they
+// are built around.  The factorisation kernels (k_ex_potrf_diag, k_ex_trsm_panel, k_ex_gemm,
+// k_ex_reduce, k_ex_trsv_diag, k_ex_trtri_diag) know nothing of the likelihood: a symmetric
+// positive definite n x n matrix, row-major, leading dimension lda, lower triangle used.
+//
+// Layout and limits (rl_exact.hip checks them and answers RL_ELIMIT / RL_ENOMEM past them):
+//   - tiles of EX_T = 64 rows / columns; every offset is 64-bit (n^2 > 2^31 from n ~ 46 000);
+//   - one n x n buffer, plus O(n * 64) workspaces: n is bounded by free device memory;
+//   - kernel descriptors: at most EX_MAX_SLOT = 32 values of k_q and dk_q / dtheta_p in all
+//     (Q + sum_q p_q), EX_MAX_COLS = 4 active input columns per kernel, D <= EX_MAX_D = 64.
+//
+// k_ex_gemm is the one update every blocked step uses (trailing SYRK of the factorisation,
+// off-diagonal blocks of the triangular solves, L^-1 and L^-T L^-1): C (+)= s A B^T on 64 x 64
+// tiles of C, A and B addressed through (row, k) strides so that transposed operands need no
+// copy.  On gfx950 the tile runs on v_mfma_f64_16x16x4_f64 (four waves, a 32 x 32 quadrant
+// each); under RL_EMU (tests/emu) a thread sums 16 entries of the tile itself -- the matrix-core
+// body is exercised only by the GPU tests.
+#pragma once
+#include "rl_device.h"
+
+#define EX_T 64
+#define EX_KC 32                    // k columns of A and B staged in LDS per step
+#define EX_LDK (EX_KC + 1)          // padded LDS row (odd: rows of a quarter wave on other banks)
+#define EX_LDT (EX_T + 1)
+#define EX_MAX_SLOT 32
+#define EX_MAX_COLS 4
+#define EX_MAX_D 64
+
+#define EX_RBF 0
+#define EX_MATERN32 1
+#define EX_STDPERIODIC 2
+#define EX_SCALED 16
+
+#if !defined(RL_EMU)
+typedef double ex_d4 __attribute__((ext_vector_type(4)));
+#endif
+
+// not a positive finite number (NaN included)
+__device__ __forceinline__ bool ex_bad_pivot(double p) { return !(p > 0.0 && p <= 1.7976931348623157e308); }
+
+// ---------------------------------------------------------------------------
+// one stationary kernel at distance r: v[0] = k(r), v[1 ..] = dk / dtheta_p in the order of
+// runlmc_amd/kern/stationary.py (kernel_gradient), the same formulas term by term.
+// prm: [inverse lengthscale, period, scale, -].  Returns the number of derivatives.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int ex_eval(int kind, const double* prm, double r, double v[4]) {
+    const double g = prm[0];
+    int np;
+    switch (kind & 15) {
+    case EX_RBF: {
+        const double sq = r * r;
+        const double e = exp(-0.5 * sq * g);
+        v[0] = e;
+        v[1] = e * (-0.5 * sq);
+        np = 1;
+        break;
+    }
+    case EX_MATERN32: {
+        const double root3r = r * 1.7320508075688772;
+        const double s = root3r * g;
+        const double e = exp(-s);
+        v[0] = (1.0 + s) * e;
+        v[1] = (1.0 + s) * (-root3r * e) + root3r * e;
+        np = 1;
+        break;
+    }
+    default: {      // EX_STDPERIODIC
+        const double T = prm[1];
+        const double arg = 3.141592653589793 / T * r;
+        const double s = sin(arg);
+        const double ds = cos(arg) * arg * (-1.0 / T * g);
+        const double sq = s * s;
+        const double e = exp(-0.5 * sq * g);
+        v[0] = log(T) < -200.0 ? __builtin_nan("") : e;     // stationary.py: from_dist
+        v[1] = e * (-0.5 * sq);
+        v[2] = e * (-1.0 * s * ds);
+        np = 2;
+        break;
+    }
+    }
+    if (kind & EX_SCALED) {
+        const double c = prm[2];
+        v[np + 1] = v[0];
+        for (int p = 1; p <= np; ++p) v[p] = c * v[p];
+        v[0] = c * v[0];
+        ++np;
+    }
+    return np;
+}
+
+// number of parameters of a kernel kind (derivatives ex_eval returns)
+__device__ __host__ __forceinline__ int ex_nder(int kind) {
+    return ((kind & 15) == EX_STDPERIODIC ? 2 : 1) + ((kind & EX_SCALED) ? 1 : 0);
+}
+
+__device__ __forceinline__ double ex_dist(const double* xa, const double* xb, const int* cols) {
+    double s = 0.0;
+    for (int c = 0; c < EX_MAX_COLS; ++c) {
+        const int col = cols[c];
+        if (col < 0) break;
+        const double d = xa[col] - xb[col];
+        s += d * d;
+    }
+    return sqrt(s);
+}
+
+// ---------------------------------------------------------------------------
+// out[i][j] = sum_q B_q[oa(i), ob(j)] k_q(r_q(xa_i, xb_j))  (+ noise[oa(i)] where i + diag_off == j)
+// for i < nrows, j < ncols; lower != 0 skips tiles above the diagonal.  grid (ceil(ncols / 64),
+// ceil(nrows / 64)), block 256: a thread fills 16 entries of a 64 x 64 tile, rows of 64
+// consecutive columns per quarter of the block.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_ex_assemble(double* __restrict__ out, long long ldo, int nrows, int ncols,
+              const double* __restrict__ Xa, const int* __restrict__ oa,
+              const double* __restrict__ Xb, const int* __restrict__ ob, int P, int Q,
+              const int* __restrict__ kinds, const double* __restrict__ prm,
+              const int* __restrict__ cols, const double* __restrict__ Bm, int D,
+              const double* __restrict__ noise, int diag_off, int lower) {
+    if (lower && blockIdx.x > blockIdx.y) return;
+    const int i0 = blockIdx.y * EX_T, j0 = blockIdx.x * EX_T;
+    for (int u = 0; u < 16; ++u) {
+        const int e = threadIdx.x + 256 * u;
+        const int i = i0 + e / EX_T, j = j0 + e % EX_T;
+        if (i >= nrows || j >= ncols) continue;
+        const int a = oa[i], b = ob[j];
+        double acc = 0.0;
+        for (int q = 0; q < Q; ++q) {
+            double v[4];
+            const double r = ex_dist(Xa + (long long)i * P, Xb + (long long)j * P, cols + q * EX_MAX_COLS);
+            ex_eval(kinds[q], prm + 4 * q, r, v);
+            acc += Bm[((long long)q * D + a) * D + b] * v[0];
+        }
+        if (noise && i + diag_off == j) acc += noise[a];
+        out[(long long)i * ldo + j] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Cholesky of the nk x nk diagonal block at (k0, k0) in one workgroup (LDS), in place (lower).
+// logd[k0 + r] = log L_rr.  The first column whose pivot is not a positive finite number goes to
+// *flag (if smaller than what is there: blocks run in order, one workgroup each); the
+// factorisation goes on through NaNs -- nothing traps.  grid 1, block 256.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_ex_potrf_diag(double* __restrict__ A, long long lda, int k0, int nk, double* __restrict__ logd,
+                int* __restrict__ flag) {
+    RL_SMEM(smem);
+    double* s = reinterpret_cast<double*>(smem);       // [64][65]
+    const int tid = threadIdx.x;
+    double* base = A + (long long)k0 * lda + k0;
+    for (int e = tid; e < nk * nk; e += 256) {
+        const int r = e / nk, c = e % nk;
+        s[r * EX_LDT + c] = c <= r ? base[(long long)r * lda + c] : 0.0;
+    }
+    __syncthreads();
+    for (int j = 0; j < nk; ++j) {
+        const double piv = s[j * EX_LDT + j];
+        const double d = sqrt(piv);
+        if (tid == 0 && ex_bad_pivot(piv) && *flag > k0 + j) *flag = k0 + j;
+        if (tid > j && tid < nk) s[tid * EX_LDT + j] /= d;
+        __syncthreads();
+        const int m = nk - j - 1;
+        for (int e = tid; e < m * m; e += 256) {
+            const int r = j + 1 + e / m, c = j + 1 + e % m;
+            if (c <= r) s[r * EX_LDT + c] -= s[r * EX_LDT + j] * s[c * EX_LDT + j];
+        }
+        if (tid == 0) s[j * EX_LDT + j] = d;
+        __syncthreads();
+    }
+    for (int e = tid; e < nk * nk; e += 256) {
+        const int r = e / nk, c = e % nk;
+        if (c <= r) base[(long long)r * lda + c] = s[r * EX_LDT + c];
+    }
+    if (tid < nk) logd[k0 + tid] = log(s[tid * EX_LDT + tid]);
+}
+
+// ---------------------------------------------------------------------------
+// Panel solve below a factored diagonal block: rows r0 .. r0 + nrows - 1, columns k0 .. k0 + nk - 1
+// become  A L_kk^-T.  One 64-row tile per workgroup (block 64: a thread solves its row).
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(64)
+k_ex_trsm_panel(double* __restrict__ A, long long lda, int k0, int nk, int r0, int nrows) {
+    RL_SMEM(smem);
+    double* L = reinterpret_cast<double*>(smem);       // [64][65]
+    double* X = L + EX_T * EX_LDT;                     // [64][65]
+    const int tid = threadIdx.x;
+    const int row0 = r0 + blockIdx.x * EX_T;
+    const int rows = nrows - blockIdx.x * EX_T < EX_T ? nrows - blockIdx.x * EX_T : EX_T;
+    const double* Lg = A + (long long)k0 * lda + k0;
+    double* Xg = A + (long long)row0 * lda + k0;
+    for (int e = tid; e < nk * nk; e += 64) {
+        const int r = e / nk, c = e % nk;
+        L[r * EX_LDT + c] = c <= r ? Lg[(long long)r * lda + c] : 0.0;
+    }
+    for (int e = tid; e < rows * nk; e += 64) {
+        const int r = e / nk, c = e % nk;
+        X[r * EX_LDT + c] = Xg[(long long)r * lda + c];
+    }
+    __syncthreads();
+    if (tid < rows) {
+        double* x = X + tid * EX_LDT;
+        for (int c = 0; c < nk; ++c) {
+            double v = x[c];
+            for (int t = 0; t < c; ++t) v -= x[t] * L[c * EX_LDT + t];
+            x[c] = v / L[c * EX_LDT + c];
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < rows * nk; e += 64) {
+        const int r = e / nk, c = e % nk;
+        Xg[(long long)r * lda + c] = X[r * EX_LDT + c];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Inverse of the lower nk x nk diagonal block at (j0, j0), in place, strict upper part of the
+// block set to 0 (the blocked L^-1 and L^-T L^-1 read whole diagonal tiles).  grid 1, block 64:
+// thread c forms column c by forward substitution.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(64)
+k_ex_trtri_diag(double* __restrict__ A, long long lda, int j0, int nk) {
+    RL_SMEM(smem);
+    double* L = reinterpret_cast<double*>(smem);       // [64][65]
+    double* W = L + EX_T * EX_LDT;
+    const int tid = threadIdx.x;
+    double* base = A + (long long)j0 * lda + j0;
+    for (int e = tid; e < nk * nk; e += 64) {
+        const int r = e / nk, c = e % nk;
+        L[r * EX_LDT + c] = c <= r ? base[(long long)r * lda + c] : 0.0;
+    }
+    __syncthreads();
+    if (tid < nk) {
+        const int c = tid;
+        for (int r = 0; r < c; ++r) W[r * EX_LDT + c] = 0.0;
+        W[c * EX_LDT + c] = 1.0 / L[c * EX_LDT + c];
+        for (int r = c + 1; r < nk; ++r) {
+            double v = 0.0;
+            for (int t = c; t < r; ++t) v += L[r * EX_LDT + t] * W[t * EX_LDT + c];
+            W[r * EX_LDT + c] = -v / L[r * EX_LDT + r];
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < nk * nk; e += 64) {
+        const int r = e / nk, c = e % nk;
+        base[(long long)r * lda + c] = W[r * EX_LDT + c];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Triangular solve of the diagonal block (k0, k0) for many right-hand sides stored as rows:
+// R[v][k0 .. k0 + nk) := L_kk^-1 (trans = 0) or L_kk^-T (trans = 1) of itself, v < nrhs.
+// grid ceil(nrhs / 64), block 64: a thread solves one right-hand side.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(64)
+k_ex_trsv_diag(const double* __restrict__ A, long long lda, int k0, int nk, double* __restrict__ R,
+               long long ldr, int nrhs, int trans) {
+    RL_SMEM(smem);
+    double* L = reinterpret_cast<double*>(smem);
+    double* X = L + EX_T * EX_LDT;
+    const int tid = threadIdx.x;
+    const int v0 = blockIdx.x * EX_T;
+    const int nv = nrhs - v0 < EX_T ? nrhs - v0 : EX_T;
+    const double* Lg = A + (long long)k0 * lda + k0;
+    for (int e = tid; e < nk * nk; e += 64) {
+        const int r = e / nk, c = e % nk;
+        L[r * EX_LDT + c] = c <= r ? Lg[(long long)r * lda + c] : 0.0;
+    }
+    for (int e = tid; e < nv * nk; e += 64) {
+        const int v = e / nk, c = e % nk;
+        X[v * EX_LDT + c] = R[(long long)(v0 + v) * ldr + k0 + c];
+    }
+    __syncthreads();
+    if (tid < nv) {
+        double* x = X + tid * EX_LDT;
+        if (!trans) {
+            for (int c = 0; c < nk; ++c) {
+                double s = x[c];
+                for (int t = 0; t < c; ++t) s -= L[c * EX_LDT + t] * x[t];
+                x[c] = s / L[c * EX_LDT + c];
+            }
+        } else {
+            for (int c = nk - 1; c >= 0; --c) {
+                double s = x[c];
+                for (int t = c + 1; t < nk; ++t) s -= L[t * EX_LDT + c] * x[t];
+                x[c] = s / L[c * EX_LDT + c];
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < nv * nk; e += 64) {
+        const int v = e / nk, c = e % nk;
+        R[(long long)(v0 + v) * ldr + k0 + c] = X[v * EX_LDT + c];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// k_ex_gemm: for the 64 x 64 tile (blockIdx.y, blockIdx.x) of an M x N result
+//   acc[i][j] = sum_{k in split z} A(i, k) B(j, k),   A(i, k) = A[i sai + k sak], B(j, k) = B[j sbj + k sbk]
+// over k in [z kchunk, min(K, (z + 1) kchunk)), cut at k < 64 (tile row + 1) when a_lower (A lower
+// triangular with explicit zeros above the diagonal of its diagonal tiles).  Then
+//   P == NULL:  C[i ldc + j] = (beta ? C : 0) + s acc     (lower_tiles: tiles with column > row skipped)
+//   P != NULL:  P[z][i][j] = acc                           (k_ex_reduce sums the splits in order)
+// grid (ceil(N / 64), ceil(M / 64), splits), block 256, LDS 2 x 64 x EX_LDK doubles.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_ex_gemm(double* __restrict__ C, long long ldc, const double* __restrict__ A, long long sai,
+          long long sak, const double* __restrict__ B, long long sbj, long long sbk, int M, int N,
+          int K, int kchunk, int a_lower, double s, int beta, int lower_tiles,
+          double* __restrict__ P) {
+    const int tn = blockIdx.x, tm = blockIdx.y, z = blockIdx.z;
+    if (lower_tiles && tn > tm) return;
+    const int i0 = tm * EX_T, j0 = tn * EX_T;
+    const int kb = z * kchunk;
+    int ke = K < kb + kchunk ? K : kb + kchunk;
+    if (a_lower && ke > i0 + EX_T) ke = i0 + EX_T;
+    RL_SMEM(smem);
+    double* sA = reinterpret_cast<double*>(smem);
+    double* sB = sA + EX_T * EX_LDK;
+    const int tid = threadIdx.x;
+#if !defined(RL_EMU)
+    const int lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
+    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+    ex_d4 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[a][b] = ex_d4{0.0, 0.0, 0.0, 0.0};
+#else
+    const int er = tid >> 2, ec = (tid & 3) * 16;      // a thread: row er, columns ec .. ec + 15
+    double acc[16];
+    for (int c = 0; c < 16; ++c) acc[c] = 0.0;
+#endif
+    for (int k0 = kb; k0 < ke; k0 += EX_KC) {
+        // stage A(i0 .. +64, k0 .. +KC) and B(j0 .. +64, k0 .. +KC), the unit-stride index fastest
+        for (int e = tid; e < EX_T * EX_KC; e += 256) {
+            int r, k;
+            if (sak == 1) { r = e / EX_KC; k = e % EX_KC; } else { k = e / EX_T; r = e % EX_T; }
+            const int gi = i0 + r, gk = k0 + k;
+            sA[r * EX_LDK + k] = gi < M && gk < ke ? A[(long long)gi * sai + (long long)gk * sak] : 0.0;
+            if (sbk == 1) { r = e / EX_KC; k = e % EX_KC; } else { k = e / EX_T; r = e % EX_T; }
+            const int gj = j0 + r, gk2 = k0 + k;
+            sB[r * EX_LDK + k] = gj < N && gk2 < ke ? B[(long long)gj * sbj + (long long)gk2 * sbk] : 0.0;
+        }
+        __syncthreads();
+#if !defined(RL_EMU)
+#pragma unroll
+        for (int kk = 0; kk < EX_KC; kk += 4) {
+            const double a0 = sA[(wm + li) * EX_LDK + kk + lk];
+            const double a1 = sA[(wm + 16 + li) * EX_LDK + kk + lk];
+            const double b0 = sB[(wn + li) * EX_LDK + kk + lk];
+            const double b1 = sB[(wn + 16 + li) * EX_LDK + kk + lk];
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+        }
+#else
+        for (int c = 0; c < 16; ++c)
+            for (int kk = 0; kk < EX_KC; ++kk) acc[c] += sA[er * EX_LDK + kk] * sB[(ec + c) * EX_LDK + kk];
+#endif
+        __syncthreads();
+    }
+    auto put = [&](int i, int j, double v) {
+        if (i >= M || j >= N) return;
+        if (P) {
+            P[(long long)z * M * N + (long long)i * N + j] = v;
+        } else {
+            double* c = C + (long long)i * ldc + j;
+            *c = beta ? *c + s * v : s * v;
+        }
+    };
+#if !defined(RL_EMU)
+    // D of v_mfma_f64_16x16x4_f64: register r of lane l = row (l >> 4) + 4 r, column l & 15
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                put(i0 + wm + 16 * a + lk + 4 * r, j0 + wn + 16 * b + li, acc[a][b][r]);
+#else
+    for (int c = 0; c < 16; ++c) put(i0 + er, j0 + ec + c, acc[c]);
+#endif
+}
+
+// C[i ldc + j] = (beta ? C : 0) + s sum_{z < nsplit} P[z][i][j], the splits in order.
+__global__ void __launch_bounds__(256)
+k_ex_reduce(double* __restrict__ C, long long ldc, const double* __restrict__ P, int M, int N,
+            int nsplit, double s, int beta) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long MN = (long long)M * N;
+    if (e >= MN) return;
+    double acc = 0.0;
+    for (int z = 0; z < nsplit; ++z) acc += P[z * MN + e];
+    const long long i = e / N, j = e % N;
+    double* c = C + i * ldc + j;
+    *c = beta ? *c + s * acc : s * acc;
+}
+
+// out[v] = sum_i V[v][i]^2 (fixed order); grid nvec, block 256.
+__global__ void __launch_bounds__(256)
+k_ex_rownorm2(const double* __restrict__ V, long long n, double* __restrict__ out) {
+    RL_SMEM(smem);
+    double* red = reinterpret_cast<double*>(smem);
+    const double* row = V + (long long)blockIdx.x * n;
+    double acc = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 256) acc += row[i] * row[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+
+// *out = 2 sum_i x[i] (fixed order); grid 1, block 256.
+__global__ void __launch_bounds__(256)
+k_ex_sum2(const double* __restrict__ x, int n, double* __restrict__ out) {
+    RL_SMEM(smem);
+    double* red = reinterpret_cast<double*>(smem);
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += x[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = 2.0 * red[0];
+}
+
+// ---------------------------------------------------------------------------
+// Gradient block sums: one workgroup per entry of `tiles` (r0, c0, a, b): a tile of rows
+// [r0, min(r0 + 64, end_a)) and columns [c0, min(c0 + 64, end_b)) of output block (a, b), a >= b,
+// of the lower triangle of Kinv.  With M_ij = alpha_i alpha_j - Kinv_ij, weight 2 for i > j
+// inside a diagonal block (the upper twin), 1 otherwise, it sums M_ij k_q(r_ij) into slot q,
+// M_ij dk_q / dtheta_p into slot dslot[q] + p, and M_ii into slot nslot (noise).  The
+// workgroup's nslot + 1 sums go to part[w][.] (fixed order: threads by index).
+// block 256, LDS (nslot + 1) x 256 doubles.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_ex_grad_tiles(const double* __restrict__ Kinv, long long n, const double* __restrict__ alpha,
+                const int* __restrict__ tiles, const int* __restrict__ bounds,
+                const double* __restrict__ X, int P, int Q, const int* __restrict__ kinds,
+                const double* __restrict__ prm, const int* __restrict__ cols,
+                const int* __restrict__ dslot, int nslot, double* __restrict__ part) {
+    RL_SMEM(smem);
+    double* red = reinterpret_cast<double*>(smem);     // [nslot + 1][256]
+    const int tid = threadIdx.x, w = blockIdx.x;
+    const int r0 = tiles[4 * w], c0 = tiles[4 * w + 1], a = tiles[4 * w + 2], b = tiles[4 * w + 3];
+    const int re = bounds[a + 1] < r0 + EX_T ? bounds[a + 1] : r0 + EX_T;
+    const int ce = bounds[b + 1] < c0 + EX_T ? bounds[b + 1] : c0 + EX_T;
+    double mw[16];
+    double dsum = 0.0;
+    for (int u = 0; u < 16; ++u) {
+        const int e = tid + 256 * u;
+        const int i = r0 + e / EX_T, j = c0 + e % EX_T;
+        double m = 0.0;
+        if (i < re && j < ce && (a != b || j <= i)) {
+            m = alpha[i] * alpha[j] - Kinv[(long long)i * n + j];
+            if (i == j) dsum += m;
+            else if (a == b) m *= 2.0;
+        }
+        mw[u] = m;
+    }
+    red[nslot * 256 + tid] = dsum;
+    for (int q = 0; q < Q; ++q) {
+        const int kind = kinds[q];
+        const double* pq = prm + 4 * q;
+        const int* cq = cols + q * EX_MAX_COLS;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        int np = 0;
+        for (int u = 0; u < 16; ++u) {
+            const int e = tid + 256 * u;
+            const int i = r0 + e / EX_T, j = c0 + e % EX_T;
+            if (i >= re || j >= ce || (a == b && j > i)) continue;
+            double v[4];
+            np = ex_eval(kind, pq, ex_dist(X + (long long)i * P, X + (long long)j * P, cq), v);
+            const double m = mw[u];
+            s0 += m * v[0];
+            s1 += m * v[1];
+            if (np > 1) s2 += m * v[2];
+            if (np > 2) s3 += m * v[3];
+        }
+        np = ex_nder(kind);       // (a thread without entries has summed zeros)
+        red[q * 256 + tid] = s0;
+        red[(dslot[q] + 0) * 256 + tid] = s1;
+        if (np > 1) red[(dslot[q] + 1) * 256 + tid] = s2;
+        if (np > 2) red[(dslot[q] + 2) * 256 + tid] = s3;
+    }
+    __syncthreads();
+    if (tid <= nslot) {
+        double acc = 0.0;
+        for (int t = 0; t < 256; ++t) acc += red[tid * 256 + t];
+        part[(long long)w * (nslot + 1) + tid] = acc;
+    }
+}
+
+// out[s][a][b] = out[s][b][a] = sum of the pair's workgroups' slot s (in order), s < nslot;
+// out[nslot D^2 + a] = noise slot of pair (a, a).  grid D (D + 1) / 2 pairs, block 64.
+__global__ void __launch_bounds__(64)
+k_ex_grad_reduce(const double* __restrict__ part, const int* __restrict__ pair_start, int D,
+                 int nslot, double* __restrict__ out) {
+    const int p = blockIdx.x;
+    int a = 0;
+    while ((a + 1) * (a + 2) / 2 <= p) ++a;
+    const int b = p - a * (a + 1) / 2;
+    for (int s = threadIdx.x; s <= nslot; s += 64) {
+        double acc = 0.0;
+        for (int w = pair_start[p]; w < pair_start[p + 1]; ++w) acc += part[(long long)w * (nslot + 1) + s];
+        if (s < nslot) {
+            out[((long long)s * D + a) * D + b] = acc;
+            out[((long long)s * D + b) * D + a] = acc;
+        } else if (a == b) {
+            out[(long long)nslot * D * D + a] = acc;
+        }
+    }
+}

@@ -1,0 +1,496 @@
+// Exact (dense) LMC likelihood on the device: the handle rl_exact of include/runlmc_hip.h.
+// Kernels: rl_exact.h.  Every step is fp64; the n x n matrix lives in ONE device buffer that is
+// K, then its Cholesky factor L, then (for gradients) the lower triangle of K^-1.
+#include "rl_host.h"
+#include "rl_exact.h"
+
+enum { EX_EMPTY = 0, EX_SET, EX_ASSEMBLED, EX_FACTORED, EX_INVERTED };
+
+struct rl_exact {
+    int device = 0, n = 0, P = 0, D = 0, Q = 0, nslot = 0, ncu = 1;
+    int state = EX_EMPTY;
+    double* A = nullptr;            // n x n
+    double* X = nullptr;            // n x P
+    int* out_of = nullptr;          // n: output of each row
+    int* bounds = nullptr;          // D + 1 row offsets of the outputs
+    int* kinds = nullptr;           // descriptors (capacity EX_MAX_SLOT kernels)
+    double* prm = nullptr;
+    int* cols = nullptr;
+    int* dslot = nullptr;
+    double* Bm = nullptr;           // Q x D x D
+    double* noise = nullptr;        // D
+    double* logd = nullptr;         // n
+    double* scal = nullptr;         // 1
+    int* flag = nullptr;            // first bad pivot
+    double* ws = nullptr;           // split-k partial sums / gradient partials
+    size_t ws_cap = 0;
+    int* tiles = nullptr;           // gradient workgroups (r0, c0, a, b)
+    int* pair_start = nullptr;
+    int ntiles = 0;
+    double* gout = nullptr;         // gradient sums
+    std::vector<int> lens, hbounds;
+};
+
+static int ex_ws(rl_exact* h, size_t doubles) {
+    if (doubles <= h->ws_cap) return RL_OK;
+    if (h->ws) RL_HIP(hipFree(h->ws));
+    h->ws = nullptr;
+    h->ws_cap = 0;
+    if (hipMalloc((void**)&h->ws, doubles * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RL_ENOMEM, "rl_exact: no device memory for a workspace of " +
+                                   std::to_string(doubles * 8 >> 20) + " MB");
+    }
+    h->ws_cap = doubles;
+    return RL_OK;
+}
+
+static inline int ex_tiles(long long v) { return (int)((v + EX_T - 1) / EX_T); }
+static const size_t kGemmLds = 2 * EX_T * EX_LDK * sizeof(double);
+static const size_t kTileLds = 2 * EX_T * EX_LDT * sizeof(double);
+
+// C (+)= s A B^T through k_ex_gemm (see rl_exact.h).  via_partials: the result goes through the
+// split-k workspace and k_ex_reduce (needed when C overlaps A or B); otherwise K is split only
+// when the tiles alone leave the chip idle.
+static int ex_gemm(rl_exact* h, hipStream_t st, double* C, long long ldc, const double* A,
+                   long long sai, long long sak, const double* B, long long sbj, long long sbk,
+                   int M, int N, int K, double s, int beta, int lower_tiles, int a_lower,
+                   bool via_partials) {
+    if (M <= 0 || N <= 0) return RL_OK;
+    const int tm = ex_tiles(M), tn = ex_tiles(N);
+    const long long ntile = lower_tiles ? (long long)tm * (tm + 1) / 2 : (long long)tm * tn;
+    const long long target = 2LL * h->ncu;
+    int nsplit = 1;
+    if (!lower_tiles && ntile < target) {
+        const long long want = (target + ntile - 1) / ntile;
+        const int kmax = ex_tiles(K);
+        nsplit = (int)(want < kmax ? want : kmax);
+    }
+    if (nsplit < 1) nsplit = 1;
+    int kchunk = (K + nsplit - 1) / nsplit;
+    kchunk = (kchunk + EX_KC - 1) / EX_KC * EX_KC;
+    if (kchunk < EX_KC) kchunk = EX_KC;
+    nsplit = (K + kchunk - 1) / kchunk;
+    if (nsplit < 1) nsplit = 1;
+    if (nsplit == 1 && !via_partials) {
+        RL_LAUNCH(k_ex_gemm, dim3(tn, tm, 1), dim3(256), kGemmLds, st, C, ldc, A, sai, sak, B, sbj,
+                  sbk, M, N, K, kchunk, a_lower, s, beta, lower_tiles, (double*)nullptr);
+        RL_HIP(hipGetLastError());
+        return RL_OK;
+    }
+    RL_TRY(ex_ws(h, (size_t)nsplit * M * N));
+    RL_LAUNCH(k_ex_gemm, dim3(tn, tm, nsplit), dim3(256), kGemmLds, st, C, ldc, A, sai, sak, B, sbj,
+              sbk, M, N, K, kchunk, a_lower, s, beta, 0, h->ws);
+    RL_HIP(hipGetLastError());
+    const long long MN = (long long)M * N;
+    RL_LAUNCH(k_ex_reduce, dim3((unsigned)((MN + 255) / 256)), dim3(256), 0, st, C, ldc,
+              (const double*)h->ws, M, N, nsplit, s, beta);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+// rows R[v][.] (v < nrhs, leading dimension n) := L^-1 R[v]  (then L^-T when both)
+static int ex_trsv(rl_exact* h, hipStream_t st, double* R, int nrhs, bool forward, bool backward) {
+    const int n = h->n, nb = ex_tiles(n);
+    const dim3 g(ex_tiles(nrhs));
+    if (forward) {
+        for (int k = 0; k < nb; ++k) {
+            const int k0 = k * EX_T, nk = std::min(EX_T, n - k0), rest = n - k0 - nk;
+            RL_LAUNCH(k_ex_trsv_diag, g, dim3(64), kTileLds, st, (const double*)h->A, (long long)n,
+                      k0, nk, R, (long long)n, nrhs, 0);
+            RL_HIP(hipGetLastError());
+            RL_TRY(ex_gemm(h, st, R + k0 + nk, n, R + k0, n, 1, h->A + (long long)(k0 + nk) * n + k0,
+                           n, 1, nrhs, rest, nk, -1.0, 1, 0, 0, false));
+        }
+    }
+    if (backward) {
+        for (int k = nb - 1; k >= 0; --k) {
+            const int k0 = k * EX_T, nk = std::min(EX_T, n - k0);
+            RL_LAUNCH(k_ex_trsv_diag, g, dim3(64), kTileLds, st, (const double*)h->A, (long long)n,
+                      k0, nk, R, (long long)n, nrhs, 1);
+            RL_HIP(hipGetLastError());
+            RL_TRY(ex_gemm(h, st, R, n, R + k0, n, 1, h->A + (long long)k0 * n, 1, n, nrhs, k0, nk,
+                           -1.0, 1, 0, 0, false));
+        }
+    }
+    return RL_OK;
+}
+
+// K(Xa, X) (+ noise on the diagonal i + diag_off == j) of nrows rows into `out` (nrows x n)
+static int ex_cross(rl_exact* h, hipStream_t st, double* out, const double* Xa, const int* oa,
+                    int nrows, const double* noise, int diag_off) {
+    if (nrows <= 0) return RL_OK;
+    RL_LAUNCH(k_ex_assemble, dim3(ex_tiles(h->n), ex_tiles(nrows)), dim3(256), 0, st, out,
+              (long long)h->n, nrows, h->n, Xa, oa, (const double*)h->X, (const int*)h->out_of,
+              h->P, h->Q, (const int*)h->kinds, (const double*)h->prm, (const int*)h->cols,
+              (const double*)h->Bm, h->D, noise, diag_off, 0);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+extern "C" int rl_exact_create(int device, int n, int P, rl_exact** out) {
+    if (!out) return fail(RL_EINVAL, "rl_exact_create: out is NULL");
+    *out = nullptr;
+    if (n < 1 || P < 1) return fail(RL_EINVAL, "rl_exact_create: n and P must be >= 1");
+    if ((long long)n * P > (1LL << 31)) return fail(RL_ELIMIT, "rl_exact_create: n * P too large");
+    RL_HIP(hipSetDevice(device));
+    rl_exact* h = new rl_exact;
+    HandleGuard<rl_exact, rl_exact_destroy> guard(h);
+    h->device = device;
+    h->n = n;
+    h->P = P;
+    hipDeviceProp_t prop;
+    RL_HIP(hipGetDeviceProperties(&prop, device));
+    h->ncu = std::max(1, prop.multiProcessorCount);
+    RL_HIP(hipMalloc((void**)&h->X, (size_t)n * P * sizeof(double)));
+    RL_HIP(hipMalloc((void**)&h->out_of, (size_t)n * sizeof(int)));
+    RL_HIP(hipMalloc((void**)&h->bounds, (EX_MAX_D + 1) * sizeof(int)));
+    RL_HIP(hipMalloc((void**)&h->kinds, EX_MAX_SLOT * sizeof(int)));
+    RL_HIP(hipMalloc((void**)&h->prm, EX_MAX_SLOT * 4 * sizeof(double)));
+    RL_HIP(hipMalloc((void**)&h->cols, EX_MAX_SLOT * EX_MAX_COLS * sizeof(int)));
+    RL_HIP(hipMalloc((void**)&h->dslot, EX_MAX_SLOT * sizeof(int)));
+    RL_HIP(hipMalloc((void**)&h->Bm, (size_t)EX_MAX_SLOT * EX_MAX_D * EX_MAX_D * sizeof(double)));
+    RL_HIP(hipMalloc((void**)&h->noise, EX_MAX_D * sizeof(double)));
+    RL_HIP(hipMalloc((void**)&h->logd, (size_t)n * sizeof(double)));
+    RL_HIP(hipMalloc((void**)&h->scal, sizeof(double)));
+    RL_HIP(hipMalloc((void**)&h->flag, sizeof(int)));
+    RL_HIP(hipMalloc((void**)&h->gout,
+                     ((size_t)EX_MAX_SLOT * EX_MAX_D * EX_MAX_D + EX_MAX_D) * sizeof(double)));
+    (void)hipFuncSetAttribute((const void*)k_ex_grad_tiles,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (EX_MAX_SLOT + 1) * 256 * (int)sizeof(double));
+    *out = guard.release();
+    return RL_OK;
+}
+
+extern "C" int rl_exact_destroy(rl_exact* h) {
+    if (!h) return RL_OK;
+    (void)hipSetDevice(h->device);
+    for (void* p : {(void*)h->A, (void*)h->X, (void*)h->out_of, (void*)h->bounds, (void*)h->kinds,
+                    (void*)h->prm, (void*)h->cols, (void*)h->dslot, (void*)h->Bm, (void*)h->noise,
+                    (void*)h->logd, (void*)h->scal, (void*)h->flag, (void*)h->ws, (void*)h->tiles,
+                    (void*)h->pair_start, (void*)h->gout})
+        if (p) (void)hipFree(p);
+    delete h;
+    return RL_OK;
+}
+
+extern "C" int rl_exact_set(rl_exact* h, const double* X, const int* lens, int D, int Q,
+                            const int* kinds, const double* params, const int* active_cols,
+                            const double* B, const double* noise) {
+    if (!h || !X || !lens || !kinds || !params || !active_cols || !B || !noise)
+        return fail(RL_EINVAL, "rl_exact_set: NULL argument");
+    if (D < 1 || Q < 1) return fail(RL_EINVAL, "rl_exact_set: D and Q must be >= 1");
+    if (D > EX_MAX_D) return fail(RL_ELIMIT, "rl_exact_set: D > 64 outputs");
+    long long total = 0;
+    for (int d = 0; d < D; ++d) {
+        if (lens[d] < 0) return fail(RL_EINVAL, "rl_exact_set: negative output length");
+        total += lens[d];
+    }
+    if (total != h->n)
+        return fail(RL_EINVAL, "rl_exact_set: lens sum to " + std::to_string(total) + ", handle has n = " +
+                                   std::to_string(h->n));
+    int nslot = Q;
+    std::vector<int> dslot(Q), cols((size_t)Q * EX_MAX_COLS);
+    for (int q = 0; q < Q; ++q) {
+        const int base = kinds[q] & ~EX_SCALED;
+        if (base != EX_RBF && base != EX_MATERN32 && base != EX_STDPERIODIC)
+            return fail(RL_EINVAL, "rl_exact_set: unknown kernel kind " + std::to_string(kinds[q]));
+        dslot[q] = nslot;
+        nslot += ex_nder(kinds[q]);
+        int nc = 0;
+        for (int c = 0; c < EX_MAX_COLS; ++c) {
+            const int col = active_cols[q * EX_MAX_COLS + c];
+            if (col >= h->P) return fail(RL_EINVAL, "rl_exact_set: active column beyond P");
+            if (col < 0) break;
+            ++nc;
+        }
+        if (nc == 0) return fail(RL_EINVAL, "rl_exact_set: a kernel without active columns");
+        for (int c = 0; c < EX_MAX_COLS; ++c) cols[q * EX_MAX_COLS + c] = c < nc ? active_cols[q * EX_MAX_COLS + c] : -1;
+    }
+    if (nslot > EX_MAX_SLOT)
+        return fail(RL_ELIMIT, "rl_exact_set: Q + sum of kernel parameters = " + std::to_string(nslot) +
+                                   " > 32");
+    RL_HIP(hipSetDevice(h->device));
+    std::vector<int> out_of(h->n), bounds(D + 1, 0);
+    for (int d = 0, i = 0; d < D; ++d) {
+        for (int k = 0; k < lens[d]; ++k) out_of[i++] = d;
+        bounds[d + 1] = bounds[d] + lens[d];
+    }
+    RL_HIP(hipMemcpy(h->X, X, (size_t)h->n * h->P * sizeof(double), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->out_of, out_of.data(), (size_t)h->n * sizeof(int), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->bounds, bounds.data(), (D + 1) * sizeof(int), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->kinds, kinds, Q * sizeof(int), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->prm, params, (size_t)Q * 4 * sizeof(double), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->cols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->dslot, dslot.data(), Q * sizeof(int), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->Bm, B, (size_t)Q * D * D * sizeof(double), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->noise, noise, D * sizeof(double), hipMemcpyHostToDevice));
+    // gradient workgroups: tiles of every output block (a, b), a >= b, of the lower triangle
+    if (h->lens != std::vector<int>(lens, lens + D) || h->D != D) {
+        std::vector<int> tl, ps(1, 0);
+        for (int a = 0; a < D; ++a)
+            for (int b = 0; b <= a; ++b) {
+                for (int r0 = bounds[a]; r0 < bounds[a + 1]; r0 += EX_T)
+                    for (int c0 = bounds[b]; c0 < bounds[b + 1]; c0 += EX_T) {
+                        if (a == b && c0 - bounds[b] > r0 - bounds[a]) continue;
+                        tl.insert(tl.end(), {r0, c0, a, b});
+                    }
+                ps.push_back((int)tl.size() / 4);
+            }
+        if (h->tiles) RL_HIP(hipFree(h->tiles));
+        if (h->pair_start) RL_HIP(hipFree(h->pair_start));
+        h->tiles = nullptr;
+        h->pair_start = nullptr;
+        RL_TRY(upload(&h->tiles, tl));
+        RL_TRY(upload(&h->pair_start, ps));
+        h->ntiles = (int)tl.size() / 4;
+        h->lens.assign(lens, lens + D);
+    }
+    h->D = D;
+    h->Q = Q;
+    h->nslot = nslot;
+    h->hbounds = bounds;
+    h->state = EX_SET;
+    return RL_OK;
+}
+
+extern "C" int rl_exact_assemble(rl_exact* h) {
+    if (!h) return fail(RL_EINVAL, "rl_exact_assemble: NULL handle");
+    if (h->state < EX_SET) return fail(RL_EINVAL, "rl_exact_assemble: no parameters (rl_exact_set)");
+    RL_HIP(hipSetDevice(h->device));
+    const int n = h->n;
+    if (!h->A) {
+        const size_t bytes = (size_t)n * n * sizeof(double);
+        size_t fr = 0, tot = 0;
+        RL_HIP(hipMemGetInfo(&fr, &tot));
+        if (bytes + ((size_t)64 << 20) > fr)
+            return fail(RL_ENOMEM, "rl_exact: the " + std::to_string(n) + " x " + std::to_string(n) +
+                                       " matrix needs " + std::to_string(bytes >> 20) + " MB, " +
+                                       std::to_string(fr >> 20) + " MB free");
+        if (hipMalloc((void**)&h->A, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            h->A = nullptr;
+            return fail(RL_ENOMEM, "rl_exact: hipMalloc of the n x n matrix failed");
+        }
+    }
+    const int nb = ex_tiles(n);
+    RL_LAUNCH(k_ex_assemble, dim3(nb, nb), dim3(256), 0, (hipStream_t)0, h->A, (long long)n, n, n,
+              (const double*)h->X, (const int*)h->out_of, (const double*)h->X,
+              (const int*)h->out_of, h->P, h->Q, (const int*)h->kinds, (const double*)h->prm,
+              (const int*)h->cols, (const double*)h->Bm, h->D, (const double*)h->noise, 0, 1);
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipStreamSynchronize(0));
+    h->state = EX_ASSEMBLED;
+    return RL_OK;
+}
+
+extern "C" int rl_exact_factor(rl_exact* h, double* logdet, int* bad_col) {
+    if (!h) return fail(RL_EINVAL, "rl_exact_factor: NULL handle");
+    if (bad_col) *bad_col = -1;
+    if (h->state != EX_ASSEMBLED) RL_TRY(rl_exact_assemble(h));
+    RL_HIP(hipSetDevice(h->device));
+    const int n = h->n, nb = ex_tiles(n);
+    const hipStream_t st = 0;
+    RL_HIP(hipMemsetAsync(h->flag, 0x7f, sizeof(int), st));
+    for (int k = 0; k < nb; ++k) {
+        const int k0 = k * EX_T, nk = std::min(EX_T, n - k0), r0 = k0 + nk, rest = n - r0;
+        RL_LAUNCH(k_ex_potrf_diag, dim3(1), dim3(256), EX_T * EX_LDT * sizeof(double), st, h->A,
+                  (long long)n, k0, nk, h->logd, h->flag);
+        RL_HIP(hipGetLastError());
+        if (rest == 0) break;
+        RL_LAUNCH(k_ex_trsm_panel, dim3(ex_tiles(rest)), dim3(64), kTileLds, st, h->A, (long long)n,
+                  k0, nk, r0, rest);
+        RL_HIP(hipGetLastError());
+        double* L21 = h->A + (long long)r0 * n + k0;
+        RL_TRY(ex_gemm(h, st, h->A + (long long)r0 * n + r0, n, L21, n, 1, L21, n, 1, rest, rest, nk,
+                       -1.0, 1, 1, 0, false));
+    }
+    RL_LAUNCH(k_ex_sum2, dim3(1), dim3(256), 256 * sizeof(double), st, (const double*)h->logd, n,
+              h->scal);
+    RL_HIP(hipGetLastError());
+    int flag = 0;
+    double ld = 0.0;
+    RL_HIP(hipMemcpy(&flag, h->flag, sizeof(int), hipMemcpyDeviceToHost));
+    RL_HIP(hipMemcpy(&ld, h->scal, sizeof(double), hipMemcpyDeviceToHost));
+    if (flag >= 0 && flag < n) {
+        // the handle keeps its parameters: set new ones (or the same) and factor again
+        h->state = EX_SET;
+        if (bad_col) *bad_col = flag;
+        return fail(RL_ENOTPD, "rl_exact_factor: the matrix is not positive definite: pivot of column " +
+                                   std::to_string(flag) + " is not a positive finite number");
+    }
+    if (logdet) *logdet = ld;
+    h->state = EX_FACTORED;
+    return RL_OK;
+}
+
+extern "C" int rl_exact_solve(rl_exact* h, const double* B, double* X, int nrhs, void* stream) {
+    if (!h || !B || !X) return fail(RL_EINVAL, "rl_exact_solve: NULL argument");
+    if (nrhs < 0) return fail(RL_EINVAL, "rl_exact_solve: nrhs < 0");
+    if (h->state != EX_FACTORED)
+        return fail(RL_EINVAL, "rl_exact_solve: the handle holds no Cholesky factor (rl_exact_factor)");
+    if (nrhs == 0) return RL_OK;
+    RL_HIP(hipSetDevice(h->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (X != B)
+        RL_HIP(hipMemcpyAsync(X, B, (size_t)nrhs * h->n * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return ex_trsv(h, st, X, nrhs, true, true);
+}
+
+// test rows on the device: X (nt x P) and their outputs
+static int ex_upload_test(rl_exact* h, const double* Xt, const int* tlens, double** dX, int** dO, int* nt) {
+    long long total = 0;
+    for (int d = 0; d < h->D; ++d) {
+        if (tlens[d] < 0) return fail(RL_EINVAL, "rl_exact: negative test length");
+        total += tlens[d];
+    }
+    if (total > (1LL << 30)) return fail(RL_ELIMIT, "rl_exact: too many test points");
+    *nt = (int)total;
+    std::vector<int> o((size_t)total);
+    for (int d = 0, i = 0; d < h->D; ++d)
+        for (int k = 0; k < tlens[d]; ++k) o[i++] = d;
+    RL_HIP(hipMalloc((void**)dX, std::max<size_t>(1, (size_t)total * h->P) * sizeof(double)));
+    RL_HIP(hipMalloc((void**)dO, std::max<size_t>(1, (size_t)total) * sizeof(int)));
+    if (total) {
+        RL_HIP(hipMemcpy(*dX, Xt, (size_t)total * h->P * sizeof(double), hipMemcpyHostToDevice));
+        RL_HIP(hipMemcpy(*dO, o.data(), (size_t)total * sizeof(int), hipMemcpyHostToDevice));
+    }
+    return RL_OK;
+}
+
+struct ExTmp {
+    void* p[3] = {nullptr, nullptr, nullptr};
+    ~ExTmp() { for (void* q : p) if (q) (void)hipFree(q); }
+};
+
+// rows of the cross-covariance per chunk: at most 256 MB of them on the device at once
+static int ex_chunk_rows(const rl_exact* h) {
+    const long long r = ((long long)256 << 20) / (8LL * h->n);
+    return (int)std::max(1LL, std::min(r, (long long)1 << 20));
+}
+
+static int ex_cross_rows(rl_exact* h, const double* Xt, const int* tlens, const double* noise,
+                         double* out_host, double* var_out) {
+    if (h->state < EX_SET) return fail(RL_EINVAL, "rl_exact: no parameters (rl_exact_set)");
+    RL_HIP(hipSetDevice(h->device));
+    ExTmp t;
+    int nt = 0;
+    if (Xt) {
+        RL_TRY(ex_upload_test(h, Xt, tlens, (double**)&t.p[0], (int**)&t.p[1], &nt));
+    } else {
+        nt = h->n;
+    }
+    if (nt == 0) return RL_OK;
+    const int rows = std::min(nt, ex_chunk_rows(h));
+    if (hipMalloc(&t.p[2], (size_t)rows * h->n * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RL_ENOMEM, "rl_exact: no device memory for the cross-covariance");
+    }
+    double* V = (double*)t.p[2];
+    double* norms = nullptr;
+    if (var_out) RL_TRY(ex_ws(h, (size_t)rows));
+    for (int r0 = 0; r0 < nt; r0 += rows) {
+        const int nr = std::min(rows, nt - r0);
+        const double* xa = Xt ? (const double*)t.p[0] + (long long)r0 * h->P : h->X + (long long)r0 * h->P;
+        const int* oa = Xt ? (const int*)t.p[1] + r0 : h->out_of + r0;
+        RL_TRY(ex_cross(h, 0, V, xa, oa, nr, noise, r0));
+        if (var_out) {
+            RL_TRY(ex_trsv(h, 0, V, nr, true, false));
+            norms = h->ws;      // (ex_trsv's updates have K <= 64: one chunk, no partials)
+            RL_LAUNCH(k_ex_rownorm2, dim3(nr), dim3(256), 256 * sizeof(double), (hipStream_t)0,
+                      (const double*)V, (long long)h->n, norms);
+            RL_HIP(hipGetLastError());
+            RL_HIP(hipMemcpy(var_out + r0, norms, (size_t)nr * sizeof(double), hipMemcpyDeviceToHost));
+        } else {
+            RL_HIP(hipMemcpy(out_host + (long long)r0 * h->n, V, (size_t)nr * h->n * sizeof(double),
+                             hipMemcpyDeviceToHost));
+        }
+    }
+    return RL_OK;
+}
+
+extern "C" int rl_exact_cross_host(rl_exact* h, const double* Xtest, const int* test_lens,
+                                   double* out) {
+    if (!h || !Xtest || !test_lens || !out) return fail(RL_EINVAL, "rl_exact_cross_host: NULL argument");
+    return ex_cross_rows(h, Xtest, test_lens, nullptr, out, nullptr);
+}
+
+extern "C" int rl_exact_dense_host(rl_exact* h, double* out) {
+    if (!h || !out) return fail(RL_EINVAL, "rl_exact_dense_host: NULL argument");
+    return ex_cross_rows(h, nullptr, nullptr, h->noise, out, nullptr);
+}
+
+extern "C" int rl_exact_explained_variance(rl_exact* h, const double* Xtest, const int* test_lens,
+                                           double* out) {
+    if (!h || !Xtest || !test_lens || !out)
+        return fail(RL_EINVAL, "rl_exact_explained_variance: NULL argument");
+    if (h->state != EX_FACTORED)
+        return fail(RL_EINVAL, "rl_exact_explained_variance: the handle holds no Cholesky factor");
+    return ex_cross_rows(h, Xtest, test_lens, nullptr, nullptr, out);
+}
+
+extern "C" int rl_exact_invert(rl_exact* h) {
+    if (!h) return fail(RL_EINVAL, "rl_exact_invert: NULL handle");
+    if (h->state == EX_INVERTED) return RL_OK;
+    if (h->state != EX_FACTORED)
+        return fail(RL_EINVAL, "rl_exact_invert: the handle holds no Cholesky factor (rl_exact_factor)");
+    RL_HIP(hipSetDevice(h->device));
+    const int n = h->n, nb = ex_tiles(n);
+    const long long ld = n;
+    double* A = h->A;
+    const hipStream_t st = 0;
+    // L^-1 in place, last block column first (LAPACK dtrtri, lower):  W_jj = L_jj^-1,
+    // W21 = -(W22 L21) W_jj  (W22 already inverted; tmp = n x 64 beside the matrix)
+    double* tmp = nullptr;
+    if (hipMalloc((void**)&tmp, (size_t)n * EX_T * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RL_ENOMEM, "rl_exact_invert: no device memory for an n x 64 panel");
+    }
+    ExTmp guard;
+    guard.p[0] = tmp;
+    for (int j = nb - 1; j >= 0; --j) {
+        const int j0 = j * EX_T, nj = std::min(EX_T, n - j0), r0 = j0 + nj, rest = n - r0;
+        RL_LAUNCH(k_ex_trtri_diag, dim3(1), dim3(64), kTileLds, st, A, ld, j0, nj);
+        RL_HIP(hipGetLastError());
+        if (rest == 0) continue;
+        RL_TRY(ex_gemm(h, st, tmp, EX_T, A + (long long)r0 * n + r0, n, 1, A + (long long)r0 * n + j0, 1, n,
+                       rest, nj, rest, 1.0, 0, 0, 1, false));
+        RL_TRY(ex_gemm(h, st, A + (long long)r0 * n + j0, n, tmp, EX_T, 1, A + (long long)j0 * n + j0, 1, n,
+                       rest, nj, nj, -1.0, 0, 0, 0, false));
+    }
+    // K^-1 = W^T W, lower, in place by block rows (LAPACK dlauum):
+    //   row block i  <-  sum_{t >= i0} W[t][i-block]^T W[t][0 .. i0 + ni)   (through the partials:
+    //   the result overwrites rows the sum reads)
+    for (int i = 0; i < nb; ++i) {
+        const int i0 = i * EX_T, ni = std::min(EX_T, n - i0);
+        RL_TRY(ex_gemm(h, st, A + (long long)i0 * n, n, A + (long long)i0 * n + i0, 1, n,
+                       A + (long long)i0 * n, 1, n, ni, i0 + ni, n - i0, 1.0, 0, 0, 0, true));
+    }
+    RL_HIP(hipStreamSynchronize(st));
+    h->state = EX_INVERTED;
+    return RL_OK;
+}
+
+extern "C" int rl_exact_grad_sums(rl_exact* h, const double* alpha, double* out) {
+    if (!h || !alpha || !out) return fail(RL_EINVAL, "rl_exact_grad_sums: NULL argument");
+    if (h->state != EX_INVERTED) RL_TRY(rl_exact_invert(h));
+    RL_HIP(hipSetDevice(h->device));
+    const int D = h->D, ns = h->nslot;
+    const hipStream_t st = 0;
+    const size_t nout = (size_t)ns * D * D + D;
+    RL_HIP(hipMemsetAsync(h->gout, 0, nout * sizeof(double), st));
+    if (h->ntiles > 0) {
+        RL_TRY(ex_ws(h, (size_t)h->ntiles * (ns + 1)));
+        RL_LAUNCH(k_ex_grad_tiles, dim3(h->ntiles), dim3(256), (size_t)(ns + 1) * 256 * sizeof(double),
+                  st, (const double*)h->A, (long long)h->n, alpha, (const int*)h->tiles,
+                  (const int*)h->bounds, (const double*)h->X, h->P, h->Q, (const int*)h->kinds,
+                  (const double*)h->prm, (const int*)h->cols, (const int*)h->dslot, ns, h->ws);
+        RL_HIP(hipGetLastError());
+    }
+    RL_LAUNCH(k_ex_grad_reduce, dim3(D * (D + 1) / 2), dim3(64), 0, st, (const double*)h->ws,
+              (const int*)h->pair_start, D, ns, h->gout);
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipMemcpy(out, h->gout, nout * sizeof(double), hipMemcpyDeviceToHost));
+    return RL_OK;
+}

@@ -1,4 +1,4 @@
-// Host-side internals shared by the three translation units of the library (round 6 split of
+// Host-side internals shared by the translation units of the library (round 6 split of
 // runlmc_hip.hip): rl_gridop.hip (grid operator, forms), rl_ski.hip (SKI operator products),
 // rl_solve.hip (Krylov and direct solves, host helpers, gradient partial sums).  Kernels come
 // from the rl_*.h headers; their non-template kernels have internal linkage, so that every

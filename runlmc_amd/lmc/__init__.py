@@ -1,0 +1,1 @@
+from .likelihood import ExactLMCLikelihood  # noqa: F401

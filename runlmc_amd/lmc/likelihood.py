@@ -1,5 +1,6 @@
 """Likelihood gradients for the LMC model (mirror of reference
-runlmc/lmc/likelihood.py:20-134), batched on the device.
+runlmc/lmc/likelihood.py:20-134), batched on the device; the exact dense likelihood
+(likelihood.py:137-217) is ExactLMCLikelihood at the end of the module.
 
 The reference builds one dK operator per hyper-parameter and spends N+1
 operator products on each (likelihood.py:48-96,112-131).  Every one of those
@@ -23,7 +24,7 @@ all-reduce of a multi-GPU step carries.
 import numpy as np
 import torch
 
-from .._native import GridOp, cross_dots, segment_dots
+from .._native import ExactOp, GridOp, cross_dots, segment_dots
 from .._lib import as_f64
 from ..util.dist import all_reduce_sum_
 
@@ -269,3 +270,117 @@ class ApproxLMCLikelihood(LMCLikelihood):
 
     def noise_gradient(self):
         return self._partials()['noise'].copy()
+
+
+class ExactLMCLikelihood(LMCLikelihood):
+    """The exact, dense LMC likelihood on the device (reference likelihood.py:137-217 with
+    exact_deriv.py:13-23): K, its Cholesky factor, alpha = K^-1 y and the four gradient families,
+    from the library's dense fp64 kernels (include/runlmc_hip.h: rl_exact_*).
+
+    The factorisation runs in the constructor; K^-1 (in place of the factor) and the gradient
+    sums on the first gradient call.  With  M = alpha alpha^T - K^-1  every derivative of the
+    reference's loops is  1/2 sum_ij M_ij dK_ij  with  dK_ij = dB[d(i), d(j)] v(r_ij),  v = k_q or
+    dk_q / dtheta_p, so the device returns one D x D block sum per v,
+        S_v[a, b] = sum_{i in a, j in b} M_ij v(r_ij),
+    and the chain rule is
+        dL/dA_q = 1/2 A_q (S_q + S_q^T)         (dB = e_j a_i^T + a_i e_j^T)
+        dL/dkappa_q = 1/2 diag(S_q)             (dB = e_i e_i^T)
+        dL/dtheta_qp = 1/2 sum_ab B_q[a, b] S_qp[a, b]
+        dL/dnoise_d = 1/2 sum_{i in d} M_ii."""
+
+    def __init__(self, functional_kernel, Xs, Ys, device_index=0):
+        super().__init__(functional_kernel, Ys)
+        fk = functional_kernel
+        X = self._stack(Xs, fk)
+        if X.shape[0] != len(self.y):
+            raise ValueError('Xs hold %d points, Ys %d' % (X.shape[0], len(self.y)))
+        self._op = ExactOp(X.shape[0], X.shape[1], device_index=device_index)
+        self._op.set(X, self.lens, fk.kernels, fk.coreg_mats(), fk.noise)
+        self._logdet = self._op.factor()
+        self._alpha_dev = self._op.solve(torch.from_numpy(as_f64(self.y)).to(self._op.device))
+        self._alpha = self._alpha_dev.cpu().numpy()
+        self._factored = True
+        self._K = None
+        self._parts = None
+
+    @staticmethod
+    def _stack(Xs, functional_kernel):
+        P = functional_kernel.P or 1
+        return np.vstack([np.asarray(X, dtype=np.float64).reshape(len(X), P) for X in Xs])
+
+    @property
+    def K(self):
+        """The dense exact kernel matrix (n x n, host).
+
+        .. warning:: quadratic in memory and time: built anew on the device and copied to the
+                     host on first access."""
+        if self._K is None:
+            self._K = self._op.dense()
+        return self._K
+
+    @staticmethod
+    def kernel_from_indices(Xs, Zs, functional_kernel, device_index=0):
+        """The dense, exact, noise-free LMC kernel between the points of `Xs` (rows) and `Zs`
+        (columns), one array per output each (reference likelihood.py:176-199), on the device."""
+        fk = functional_kernel
+        Z = ExactLMCLikelihood._stack(Zs, fk)
+        X = ExactLMCLikelihood._stack(Xs, fk)
+        if Z.shape[0] == 0 or X.shape[0] == 0:
+            return np.zeros((X.shape[0], Z.shape[0]))
+        op = ExactOp(Z.shape[0], Z.shape[1], device_index=device_index)
+        op.set(Z, [len(z) for z in Zs], fk.kernels, fk.coreg_mats(), np.zeros(fk.D))
+        return op.cross(X, [len(x) for x in Xs])
+
+    def _factor(self):
+        """The Cholesky factor again if the gradients replaced it by K^-1."""
+        if not self._factored:
+            self._op.factor()
+            self._factored = True
+
+    def explained_variance(self, Xs):
+        """diag(K_*X K^-1 K_X*) for test points Xs, one array per output (reference
+        interpolated_llgp.py:350-356), from the Cholesky factor on the device."""
+        self._factor()
+        fk = self.functional_kernel
+        return self._op.explained_variance(self._stack(Xs, fk), [len(x) for x in Xs])
+
+    def alpha(self):
+        return self._alpha
+
+    def log_det_K(self):
+        """2 sum log L_ii of the exact K (reference interpolated_llgp.py:262-276)."""
+        return self._logdet
+
+    def normal_quadratic(self):
+        return float(self.y.dot(self._alpha))
+
+    def log_likelihood(self):
+        n = len(self.y)
+        return -0.5 * (self._logdet + self.normal_quadratic() + n * np.log(2 * np.pi))
+
+    def _partials(self):
+        if self._parts is None:
+            self._factored = False          # K^-1 takes the factor's place
+            S, noise = self._op.grad_sums(self._alpha_dev)
+            Q = self.functional_kernel.Q
+            first = np.concatenate([[Q], Q + np.cumsum(self._op.nder)])
+            self._parts = dict(S=S[:Q], dS=[S[first[q]:first[q + 1]] for q in range(Q)],
+                               noise=noise)
+        return self._parts
+
+    def coreg_vec_gradients(self):
+        S = self._partials()['S']
+        return [0.5 * a.dot(S[q] + S[q].T)
+                for q, a in enumerate(self.functional_kernel.coreg_vecs)]
+
+    def coreg_diags_gradients(self):
+        S = self._partials()['S']
+        return [0.5 * np.diag(S[q]).copy() for q in range(self.functional_kernel.Q)]
+
+    def kernel_gradients(self):
+        dS = self._partials()['dS']
+        return [[0.5 * float(np.sum(B * Sp)) for Sp in dS[q]]
+                for q, B in enumerate(self.functional_kernel.coreg_mats())]
+
+    def noise_gradient(self):
+        return 0.5 * self._partials()['noise']

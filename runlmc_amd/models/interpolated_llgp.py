@@ -9,12 +9,17 @@ Every product, solve and gradient inside runs on the device
 
 * ``log_det_K()`` is the matrix-free stochastic-Lanczos estimate of
   log det K~ (the reference's is a dense Cholesky of the exact kernel and is
-  never on its optimiser path, interpolated_llgp.py:262-276).
+  never on its optimiser path, interpolated_llgp.py:262-276); the exact one is
+  ``ExactLMCLikelihood.log_det_K()``, the dense likelihood ``K()`` returns.
 * inputs of any dimension, each kernel acting on one or two of them (bicubic
   interpolation, BTTB kernels; kernels on different active-dimension sets get
   their own grids);
 * prediction modes: 'on-the-fly' and 'precompute' (both batched solves on the
-  device); 'exact' (dense Cholesky) is not provided.
+  device) and 'exact' (variances from the device Cholesky factor of the exact
+  kernel, runlmc_amd.lmc.ExactLMCLikelihood; any input dimension, split kernels).
+* ``metrics=True`` records ``grad_error`` against the exact likelihood's
+  gradient, as the reference does; at sizes the dense path cannot hold (device
+  memory, kernel limits) the entry is NaN and one warning is logged.
 * parameters live in one flat array in the optimiser's space; positive
   parameters go through paramz's Logexp (softplus) transform as in the
   reference (functional_kernel.py:130,185; rbf.py:33).
@@ -28,7 +33,7 @@ import scipy.spatial.distance as sdist
 from ..approx.interpolation import autogrid, multi_interpolant
 from ..approx.iterative import Iterative
 from ..lmc.grid_kernel import gen_grid_kernel
-from ..lmc.likelihood import ApproxLMCLikelihood
+from ..lmc.likelihood import ApproxLMCLikelihood, ExactLMCLikelihood
 from ..lmc.metrics import Metrics
 from ..lmc.stochastic_deriv import StochasticDerivService
 from .optimization import AdaDelta
@@ -73,7 +78,7 @@ class InterpolatedLLGP:
         self.Xs = [np.asarray(X, dtype=float).reshape(len(X), -1) for X in Xs]
         if not functional_kernel:
             raise ValueError('functional_kernel must be provided')
-        if prediction not in ('on-the-fly', 'precompute'):
+        if prediction not in ('on-the-fly', 'precompute', 'exact'):
             raise ValueError('Variance prediction method {} unrecognized'
                              .format(prediction))
         self.prediction = prediction
@@ -96,6 +101,7 @@ class InterpolatedLLGP:
         self._K = None
         self._grid_kernels = None
         self._caches = {}
+        self._exact_declined = False
         _LOG.info('InterpolatedLLGP %s fully initialized', self.name)
 
     # -- data handling (multigp.py:75-118) ----------------------------------------
@@ -225,7 +231,47 @@ class InterpolatedLLGP:
         if self.metrics is not None:
             g = self.gradient
             self.metrics.grad_norms.append(float(np.abs(g).max()))
+            self.metrics.grad_error.append(self._grad_error())
             self.metrics.log_likely.append(self.log_likelihood())
+
+    @staticmethod
+    def _grad_vector(lik):
+        """The four gradient families concatenated in the reference's order
+        (interpolated_llgp.py:230-238)."""
+        return np.concatenate((
+            np.concatenate(lik.coreg_vec_gradients()).reshape(-1),
+            np.concatenate(lik.coreg_diags_gradients()),
+            np.concatenate(lik.kernel_gradients()),
+            lik.noise_gradient()))
+
+    def _grad_error(self):
+        """|g_approx - g_exact| / |g_exact| in EVAL_NORM (interpolated_llgp.py:228-245); NaN
+        when the exact likelihood cannot be formed at this size."""
+        try:
+            exact = self._dense()
+        except (MemoryError, NotImplementedError, np.linalg.LinAlgError) as e:
+            if not self._exact_declined:
+                _LOG.warning('metrics: no exact gradient for grad_error (%s); recording NaN', e)
+                self._exact_declined = True
+            return float('nan')
+        ga, ge = self._grad_vector(self.kernel), self._grad_vector(exact)
+        return float(np.linalg.norm(ga - ge, self.EVAL_NORM) /
+                     np.linalg.norm(ge, self.EVAL_NORM))
+
+    def _dense(self):
+        """The exact likelihood for the current parameters, built once per
+        parameters_changed (reference interpolated_llgp.py:247-250)."""
+        if 'dense' not in self._caches:
+            self._caches['dense'] = ExactLMCLikelihood(
+                self._functional_kernel, self.Xs, self.Ys, device_index=self._device_index)
+        return self._caches['dense']
+
+    def K(self):
+        """The dense exact kernel matrix (reference interpolated_llgp.py:252-260).
+
+        .. warning:: quadratic in memory and time."""
+        self._ensure()
+        return self._dense().K
 
     def optimize(self, optimizer=None, **kwargs):
         """Maximise the likelihood with AdaDelta (reference multigp.py:176-197
@@ -305,6 +351,11 @@ class InterpolatedLLGP:
         sol = Iterative.solve(self._K, Kx)           # one batched device solve
         return np.einsum('ij,ij->i', Kx, np.atleast_2d(sol))
 
+    def _var_exact(self, _W, Xs):
+        """diag(K_*X K^-1 K_X*) with the exact K's Cholesky factor (reference
+        interpolated_llgp.py:350-356)."""
+        return self._dense().explained_variance(Xs)
+
     def _precomputed_nu(self):
         if 'nu' not in self._caches:
             if len(self.interpolants) != 1:
@@ -336,8 +387,8 @@ class InterpolatedLLGP:
             Ws[ad] = multi_interpolant([X[:, list(ad)] for X in Xs], *self.grid_axes[ad])
             mean += Ws[ad].dot(grid_alpha)
         native = np.repeat(self._native_variance(), lens)
-        explained = (self._var_on_the_fly if self.prediction == 'on-the-fly'
-                     else self._var_precompute)(Ws, Xs)
+        explained = {'on-the-fly': self._var_on_the_fly, 'precompute': self._var_precompute,
+                     'exact': self._var_exact}[self.prediction](Ws, Xs)
         var = native - explained
         var[var < 0] = 0
         cuts = np.cumsum(lens)[:-1]
