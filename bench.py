@@ -2,7 +2,8 @@
 """Headline benchmark: Kronecker-Toeplitz MVMs/sec + NLL-and-gradient
 wall-clock at the synthetic (D, Q, m) configurations of BASELINE.json.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5              # 1 GPU
+    python bench.py --gpus 1 --steps 20 --warmup 5              # 1 GPU, the headline alone
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full       # ... and everything else below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -16,8 +17,15 @@ collective in the product (weak scaling; value = all ranks' MVMs / max time).
 clock around the K steps, bracketed by barrier + synchronize (the device-event
 time of the same region is printed beside it as a cross-check).
 
-Extra keys of the same JSON line: the full K~ = W K_UU W^T + eps product, the
-NLL+gradient step (eps = 0.1 as the reference, and the eps = 1 control of
+A plain run does what the headline needs and no more: set-up, the W warm-up and
+K timed steps of the headline product, the outputs of --dump-outputs (which
+runs the default NLL+gradient step once for its arrays), the line.  Everything
+else is behind --full.
+
+Extra keys of the same JSON line under --full: the copy of the same vectors and
+the transform kernels beside the headline, the other kernel families, the batch
+sweep, the full K~ = W K_UU W^T + eps product, the NLL+gradient step
+(eps = 0.1 as the reference, and the eps = 1 control of
 SURVEY 8d), the same set at C2 under "c2", and `cpu_baseline` -- the oracle
 timed on this host in a child process that never touches the GPU (single-core
 grid MVMs/sec; NLL+gradient with multiprocessing.Pool(cpu_count()) over the N+1
@@ -57,6 +65,12 @@ def parse():
     ap.add_argument('--kern', default='rbf', choices=['rbf', 'periodic', 'matern', 'mix'],
                     help='kernel family of the headline (reference benchmarks/benchlib/'
                          'bench.py:94,284-297); the other three are timed under "families"')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: the copy and transform-kernel timings of the same '
+                         'vectors, the other kernel families, the batch sweep, the full operator, '
+                         'the NLL+gradient steps, the second configuration and the CPU baselines '
+                         '(minutes; the --no-* options below drop parts of it).  Without it the '
+                         'run measures the headline product alone')
     ap.add_argument('--no-families', action='store_true',
                     help='skip the product timings of the other kernel families')
     ap.add_argument('--batch', type=int, default=0,
@@ -66,7 +80,7 @@ def parse():
     ap.add_argument('--no-sweep', action='store_true',
                     help='skip the saturating-batch timings (extra keys)')
     ap.add_argument('--no-full', action='store_true',
-                    help='skip the full-operator (W K_UU W^T + eps) timing')
+                    help='skip the full-operator (W K_UU W^T + eps) timing of --full')
     ap.add_argument('--no-extra', action='store_true',
                     help='skip the second configuration (the "c2" key)')
     ap.add_argument('--no-stall', action='store_true',
@@ -97,6 +111,10 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be at least 1 and --warmup at least 0')
+    if not args.full:
+        # a plain run: the headline product (and the NLL+gradient step only for --dump-outputs)
+        args.no_families = args.no_cpu = args.no_sweep = args.no_full = True
+        args.no_extra = args.no_stall = True
     return args
 
 
@@ -749,7 +767,7 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
     }
     if traffic is not None:
         out['roofline']['traffic_GBps'] = traffic / (wall_ms * 1e-3) / 1e9
-    if headline:
+    if headline and args.full:
         # what THIS box does when it merely copies the step's vectors (a stock elementwise
         # kernel: read X once, write Y once -- the algorithmic traffic of the product), same
         # clock: the interface's 8 TB/s is `peak`, this is what a read-once / write-once
@@ -762,7 +780,7 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
             'what': 'torch.mul(X, 1.0, out=Y) on the step\'s %d x %d fp64 vectors' % tuple(X.shape)}
         out['roofline']['frac_of_copy'] = achieved / copy_gbs
 
-    if poly:
+    if poly and args.full:
         # the same product forced onto the transform (FFT) kernels, same clock:
         # what Matern / short-length-scale kernels and 2-D grids run
         g.set_form_gate(1 << 62)
@@ -806,13 +824,17 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
         out['batch_sweep'] = sweep
     del X, Y
 
-    if not args.no_nll:
+    # (a plain run takes the default step alone, and only for the arrays of --dump-outputs: on
+    # every rank, the step holds collectives)
+    if not args.no_nll and (args.full or (headline and args.dump_outputs)):
         import torch.distributed as tdist
         group = tdist.group.WORLD if (args.force_dist or world > 1) else None
 
         def rel_dist(a, b):
             return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
         for key, eps in (('nll_grad', 0.1), ('nll_grad_eps1', 1.0)):
+            if key != 'nll_grad' and not args.full:
+                continue
             pe = p if eps == 0.1 else synth.make_problem(D, Q, R, m_data, eps=eps, kern=kern)
             np.random.seed(4321)
             # the config's N probes in total, dealt round-robin to the ranks
@@ -834,6 +856,9 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
                         probes_per_rank=-(-n_probes // world),
                         probes='int64 host matrix as the reference draws it, checked and '
                                'narrowed inside the timed step')
+            if not args.full:
+                out[key] = info
+                continue
             direct = info['solver'].startswith(('direct', 'pcg'))
             if world > 1 and key == 'nll_grad':
                 # the SAME step on one rank alone (every rank runs it, no collective): what the
@@ -922,7 +947,7 @@ def bench_config(name, args, rank, world, dev, steps, warmup, headline):
                           gradient_rel_distance_to_default_step=rel_dist(grad_stall, grad_default),
                           gradient_rel_distance_to_scipy_exit_step=rel_dist(grad_kry, grad_stall))
                 out['nll_grad_to_stall'] = st
-        if name != 'c5' and world == 1:
+        if name != 'c5' and world == 1 and args.full:
             # the Krylov step run ON to the reference's tolerance: MINRES's own stopping tests
             # off (RL_MINRES_RULE), the reference's rule -- explicit residual < 1e-4 at every
             # 100th iteration, approx/iterative.py:36-42 -- ends each system; the CPU side runs

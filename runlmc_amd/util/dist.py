@@ -13,7 +13,7 @@ with one all-gather.
 
 `force_collectives(True)` makes every helper issue its collective even in a
 world of ONE rank: on a one-GPU box that is the only way to push the step's
-broadcast / all-reduce / all-gather through RCCL itself (bench.py --force-dist,
+broadcast / all-reduce / all-gather through RCCL itself (bench.py --full --force-dist,
 tests/test_gpu_multi_rank.py)."""
 import torch
 import torch.distributed as dist

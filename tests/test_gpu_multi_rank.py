@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMMON = ['--config', 'c2', '--steps', '20', '--warmup', '3', '--no-cpu', '--no-sweep',
           '--no-extra', '--no-families']
+FULL = ['--full'] + COMMON      # the NLL+gradient steps these tests read are behind --full
 
 
 def _free_port():
@@ -37,7 +38,7 @@ def _last_json(out):
 
 def test_bench_two_ranks_one_gpu():
     env = dict(os.environ, OMP_NUM_THREADS='1')
-    one = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + COMMON,
+    one = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + FULL,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env,
                          timeout=900)
     assert one.returncode == 0, one.stderr[-2000:]
@@ -46,7 +47,7 @@ def test_bench_two_ranks_one_gpu():
         [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
          '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
          os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dist-backend', 'gloo', '--same-gpu']
-        + COMMON, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
+        + FULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=900)
     assert two.returncode == 0, two.stderr[-3000:]
     j2 = _last_json(two.stdout)
     assert j2['n_gpus'] == 2 and j1['n_gpus'] == 1
@@ -72,7 +73,7 @@ def test_collectives_through_rccl_in_a_world_of_one():
     bit (a world of one changes no arithmetic)."""
     env = dict(os.environ, OMP_NUM_THREADS='1', MASTER_ADDR='127.0.0.1',
                MASTER_PORT=str(_free_port()))
-    args = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + COMMON
+    args = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + FULL
     plain = subprocess.run(args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env,
                            timeout=900)
     assert plain.returncode == 0, plain.stderr[-2000:]
@@ -121,7 +122,7 @@ def test_bench_starts_its_own_ranks():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
-                        '--dist-backend', 'gloo', '--same-gpu'] + COMMON,
+                        '--dist-backend', 'gloo', '--same-gpu'] + FULL,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env,
                        timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -16,7 +16,7 @@ fi
 # headline's three kernels (full-size launches only: the set-time verification launches the same
 # kernels on a few dozen rows)
 rm -rf /tmp/prof_c5; mkdir -p /tmp/prof_c5
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c5 -- python3 $root/bench.py --steps 50 --warmup 5 --no-cpu --no-nll --no-sweep --no-full --no-extra --no-families > /tmp/prof_c5/bench.json 2> /tmp/prof_c5/err.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c5 -- python3 $root/bench.py --full --steps 50 --warmup 5 --no-cpu --no-nll --no-sweep --no-full --no-extra --no-families > /tmp/prof_c5/bench.json 2> /tmp/prof_c5/err.txt
 cp $(find /tmp/prof_c5 -name '*kernel_stats.csv' | head -1) $out/c5_products_kernel_stats.csv
 python3 - <<PY > $out/c5_k129_poly_launch_durations.txt
 import csv,glob,collections
@@ -68,7 +68,7 @@ python3 $root/tools/k1_product_run.py 4 504 2048 20 2>/dev/null >> $out/pmc_k1_p
 rm -rf $root/gpurun_out/pmc_r05_sq_k1
 cat $out/pmc_c5_matern_summary.txt $out/pmc_k1_product_fx2007_shape_summary.txt
 # the default bench command, as the driver runs it (reads the traffic table written above)
-python3 $root/bench.py > $out/bench_default.json 2> $out/bench_default.err
+python3 $root/bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 tail -c 1500 $out/bench_default.json
 python3 $root/tools/families.py c5 2>/dev/null > $out/families_c5.txt; cat $out/families_c5.txt
 python3 $root/tools/families.py c2 2>/dev/null > $out/families_c2.txt
@@ -81,7 +81,7 @@ if [ "$mode" != "quick" ]; then
   python3 $root/tools/sweep.py matern 2>/dev/null > $out/sweep_dqm_matern.txt
   tail -9 $out/sweep_dqm_matern.txt
   for fam in periodic matern mix; do
-    python3 $root/bench.py --kern $fam --steps 20 --warmup 3 --no-families --no-sweep > $out/bench_$fam.json 2> $out/bench_$fam.err
+    python3 $root/bench.py --full --kern $fam --steps 20 --warmup 3 --no-families --no-sweep > $out/bench_$fam.json 2> $out/bench_$fam.err
     python3 -c "
 import json; d=json.load(open('$out/bench_$fam.json')); n=d['nll_grad']
 print('$fam product ms %.3f frac %.3f | nll s %.3f it %.0f | share ceiling %.2f' % (d['ms_per_step'], d['roofline']['frac'], n['seconds'], n['iterations_mean'], n.get('projected_strong_scaling_8gpu',{}).get('ceiling',0)))"

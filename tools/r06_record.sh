@@ -26,17 +26,17 @@ rm -rf $root/gpurun_out/pmc_fam
 cp $root/profiles/r06/traffic.json $out/traffic.json 2>/dev/null
 # the default bench command, as the driver runs it (reads the traffic table written above)
 cd $root
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err < /dev/null
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err < /dev/null
 tail -c 600 $out/bench_default.err
 cd /tmp
 rm -rf /tmp/prof_bench
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python3 $root/bench.py --no-cpu > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err < /dev/null
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_bench -- python3 $root/bench.py --full --no-cpu > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err < /dev/null
 f=$(find /tmp/prof_bench -name "*kernel_stats.csv" 2>/dev/null | head -1)
 if [ -n "$f" ] && [ -f "$f" ]; then cp "$f" $out/bench_default_kernel_stats.csv; fi
 # per-launch durations of the headline's three kernels (full-size launches only: the set-time verification
 # launches the same kernels on a few dozen rows)
 rm -rf /tmp/prof_c5; mkdir -p /tmp/prof_c5
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c5 -- python3 $root/bench.py --steps 50 --warmup 5 --no-cpu --no-nll --no-sweep --no-full --no-extra --no-families > /tmp/prof_c5/bench.json 2> /tmp/prof_c5/err.txt < /dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c5 -- python3 $root/bench.py --full --steps 50 --warmup 5 --no-cpu --no-nll --no-sweep --no-full --no-extra --no-families > /tmp/prof_c5/bench.json 2> /tmp/prof_c5/err.txt < /dev/null
 f=$(find /tmp/prof_c5 -name "*kernel_stats.csv" 2>/dev/null | head -1)
 if [ -n "$f" ] && [ -f "$f" ]; then cp "$f" $out/c5_products_kernel_stats.csv; fi
 python3 - <<PY > $out/c5_k129_poly_launch_durations.txt
@@ -63,7 +63,7 @@ cat $out/c5_k129_poly_launch_durations.txt
 if [ "${1:-}" != quick ]; then
   cd $root
   for k in periodic matern mix; do
-    python3 bench.py --kern $k --no-cpu --no-extra > $out/bench_$k.json 2> $out/bench_$k.err < /dev/null
+    python3 bench.py --full --kern $k --no-cpu --no-extra > $out/bench_$k.json 2> $out/bench_$k.err < /dev/null
   done
   python3 tools/families.py c5 2>/dev/null > $out/families_c5.txt < /dev/null
   python3 tools/families.py c2 2>/dev/null > $out/families_c2.txt < /dev/null
