@@ -41,11 +41,12 @@ typedef struct rl_exact rl_exact;
  * gained `method`, round 4; 3: rl_gridop_form_stats added, round 5; 4: rl_ski_factor,
  * rl_solve_direct, rl_solve_pcg, rl_ski_project,
  * rl_gridop_project, rl_gridop_set_rank_hint, rl_gridop_poly_coeffs, rl_slq_log_quadrature,
- * rl_probes_to_int8 added, round 6; 5: the rl_exact_* handle of the exact likelihood; callers
+ * rl_probes_to_int8 added, round 6; 5: the rl_exact_* handle of the exact likelihood; 6: rl_exact_cross_dev
+ * and rl_row_dots, the tiled predictive variances; callers
  * built against an older version must be rebuilt).  A binding
  * compares rl_abi_version() with the RL_ABI_VERSION it was written against before its
  * first call (runlmc_amd/_lib.py does) instead of finding out through shifted arguments. */
-#define RL_ABI_VERSION 5
+#define RL_ABI_VERSION 6
 int rl_abi_version(void);
 
 const char* rl_last_error(void);
@@ -405,6 +406,25 @@ int rl_exact_explained_variance(rl_exact* h, const double* Xtest, const int* tes
 /* The noise-free cross-covariance K(Xtest, X), out host [nt][n]
  * (ExactLMCLikelihood.kernel_from_indices, likelihood.py:176-199).  Needs only rl_exact_set.    */
 int rl_exact_cross_host(rl_exact* h, const double* Xtest, const int* test_lens, double* out);
+/* nrows of those rows, K(Xtest[row0 : row0 + nrows], X), into the DEVICE buffer out dev [nrows][n]
+ * in the operator's row order: the right-hand sides of the predictive variances, which the
+ * reference builds on the host and hands to its solver one by one
+ * (models/interpolated_llgp.py:358-397).  Xtest host [nt][P] and test_lens host [D] describe ALL
+ * test points (nt = sum test_lens), as in rl_exact_cross_host; only the window's rows are copied,
+ * during the call.  The kernel (csrc/rl_exact.h: k_ex_cross_rows, written for few rows by many
+ * columns; entries as rl_exact_cross_host's) is queued on `stream`.  Needs only rl_exact_set and
+ * allocates O(nrows P) on the handle, nothing of size n^2.  RL_EINVAL: NULL, row0 + nrows > nt,
+ * no parameters; RL_ELIMIT: P + Q D > 4096 (one test row must fit the kernel's LDS).            */
+int rl_exact_cross_dev(rl_exact* h, const double* Xtest, const int* test_lens, int row0, int nrows,
+                       double* out, void* stream);
+/* The reduction of those variances, fused: dots[v] = sum_i B[v][i] X[v][i] (the np.einsum /
+ * diagonal of interpolated_llgp.py:358-397 once X[v] = K~^-1 B[v]) and sqnorms[v] = sum_i X[v][i]^2
+ * in ONE pass over B, X dev [nvec][n]; dots, sqnorms dev [nvec]; ws dev [nvec][RL_ROW_DOTS_WS]
+ * partial sums.  Two stages in a fixed order, no atomics: bit-identical from call to call.
+ * Queued on `stream` of the current device; nvec <= 65535 (RL_ELIMIT).                          */
+#define RL_ROW_DOTS_WS 128
+int rl_row_dots(const double* B, const double* X, int nvec, long long n, double* dots,
+                double* sqnorms, double* ws, void* stream);
 /* The whole K, out host [n][n] (likelihood.py:149-151; interpolated_llgp.py:248-260).  Built
  * anew in row panels: valid in any state after rl_exact_set, O(n^2) host memory.               */
 int rl_exact_dense_host(rl_exact* h, double* out);

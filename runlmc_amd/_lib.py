@@ -74,11 +74,13 @@ _SIGNATURES = {
     'rl_exact_solve': [_vp, _vp, _vp, _i, _vp],
     'rl_exact_explained_variance': [_vp, _vp, _vp, _vp],
     'rl_exact_cross_host': [_vp, _vp, _vp, _vp],
+    'rl_exact_cross_dev': [_vp, _vp, _vp, _i, _i, _vp, _vp],
+    'rl_row_dots': [_vp, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp],
     'rl_exact_dense_host': [_vp, _vp],
     'rl_exact_invert': [_vp],
     'rl_exact_grad_sums': [_vp, _vp, _vp],
 }
-ABI_VERSION = 5      # include/runlmc_hip.h: RL_ABI_VERSION
+ABI_VERSION = 6      # include/runlmc_hip.h: RL_ABI_VERSION
 _RESTYPE = {'rl_last_error': ctypes.c_char_p, 'rl_backend': ctypes.c_char_p}
 
 

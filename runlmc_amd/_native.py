@@ -490,6 +490,22 @@ def segment_dots(lib, U, V, offsets_dev, D):
     return out
 
 
+ROW_DOTS_WS = 128       # include/runlmc_hip.h: RL_ROW_DOTS_WS
+
+
+def row_dots(lib, B, X):
+    """(dots, sqnorms) device tensors (k,): sum_i B[v, i] X[v, i] and sum_i X[v, i]^2 in one
+    pass, a fixed order of summation (rl_row_dots)."""
+    if B.shape != X.shape or B.dim() != 2:
+        raise ValueError('row_dots: B and X must be (k, n) tensors of one shape')
+    k, n = B.shape
+    out = torch.empty((2, k), dtype=torch.float64, device=B.device)
+    ws = torch.empty((max(k, 1), ROW_DOTS_WS), dtype=torch.float64, device=B.device)
+    lib.call('rl_row_dots', dev_ptr(B), dev_ptr(X), int(k), int(n), dev_ptr(out[0]),
+             dev_ptr(out[1]), dev_ptr(ws), lib.stream_ptr(B.device))
+    return out[0], out[1]
+
+
 # ---- exact (dense) likelihood: include/runlmc_hip.h rl_exact_* ----------------------------------
 RL_EXACT_SCALED = 16
 EXACT_MAX_COLS = 4
@@ -613,6 +629,23 @@ class ExactOp:
         out = np.zeros((Xt.shape[0], self.n))
         self.lib.call('rl_exact_cross_host', self._h, host_ptr(Xt), host_ptr(tl), host_ptr(out))
         return out
+
+    def cross_device(self, Xt, test_out_or_lens, row0, nrows, out=None):
+        """Rows row0 .. row0 + nrows of the noise-free K(Xt, X) as a DEVICE tensor (nrows, n):
+        rl_exact_cross_dev.  Xt (nt, P) holds all test rows, the outputs concatenated;
+        `test_out_or_lens` is their length per output (D values).  `out`: a contiguous float64
+        device tensor with room for the rows, reused from tile to tile."""
+        Xt, tl = self._rows(Xt, test_out_or_lens, 'cross_device')
+        row0, nrows = int(row0), int(nrows)
+        if out is None:
+            out = torch.empty((max(nrows, 1), self.n), dtype=torch.float64, device=self.device)
+        elif (out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous()
+              or out.numel() < max(nrows, 0) * self.n):
+            raise ValueError('out must be a contiguous float64 tensor of >= %d x %d values on %s'
+                             % (nrows, self.n, self.device))
+        self.lib.call('rl_exact_cross_dev', self._h, host_ptr(Xt), host_ptr(tl), row0, nrows,
+                      dev_ptr(out), self.lib.stream_ptr(self.device))
+        return out.reshape(-1)[:max(nrows, 0) * self.n].reshape(max(nrows, 0), self.n)
 
     def dense(self):
         """The whole K, (n, n) on the host."""

@@ -137,6 +137,119 @@ k_ex_assemble(double* __restrict__ out, long long ldo, int nrows, int ncols,
 }
 
 // ---------------------------------------------------------------------------
+// The same entries for the wide and short shape of prediction: a few hundred test rows by up to
+// 10^6 training columns.  out[t][j] = sum_q B_q[ot(t), ob(j)] k_q(r_q(xt_t, xb_j)), t < nrows,
+// j < ncols, no noise.  grid (ceil(ncols / EX_CR_COLS), ceil(nrows / rg)), block EX_CR_COLS.
+// A workgroup stages its rg test rows once in LDS -- coordinates and the Q gathered rows
+// B_q[ot(t), :] -- and, when stage_cols, the coordinates of its EX_CR_COLS training columns
+// (leading dimension ldx, odd: neighbouring threads on other banks).  A thread owns column
+// j = blockIdx.x EX_CR_COLS + threadIdx.x: it reads x_j and ob(j) once, loops over the staged
+// rows and stores out[t][j], consecutive along j across the wave.  Every entry goes through
+// ex_dist / ex_eval with the sum over q in k_ex_assemble's order.
+// LDS: rg (P + Q D) + (stage_cols ? EX_CR_COLS ldx : 0) doubles (ex_cross_rows sizes rg).
+// ---------------------------------------------------------------------------
+#define EX_CR_COLS 256
+__global__ void __launch_bounds__(EX_CR_COLS)
+k_ex_cross_rows(double* __restrict__ out, long long ldo, int nrows, int ncols, int rg,
+                const double* __restrict__ Xt, const int* __restrict__ ot,
+                const double* __restrict__ Xb, const int* __restrict__ ob, int P, int Q,
+                const int* __restrict__ kinds, const double* __restrict__ prm,
+                const int* __restrict__ cols, const double* __restrict__ Bm, int D,
+                int stage_cols, int ldx) {
+    RL_SMEM(smem);
+    double* sx = reinterpret_cast<double*>(smem);      // [rg][P]
+    double* sb = sx + (long long)rg * P;               // [rg][Q][D]
+    double* sc = sb + (long long)rg * Q * D;           // [EX_CR_COLS][ldx]
+    const int tid = threadIdx.x;
+    const int t0 = blockIdx.y * rg;
+    const int nt = nrows - t0 < rg ? nrows - t0 : rg;
+    const long long j = (long long)blockIdx.x * EX_CR_COLS + tid;
+    for (int e = tid; e < nt * P; e += EX_CR_COLS) sx[e] = Xt[(long long)t0 * P + e];
+    const int QD = Q * D;
+    for (int e = tid; e < nt * QD; e += EX_CR_COLS) {
+        const int t = e / QD, r = e % QD, q = r / D, b = r % D;
+        sb[e] = Bm[((long long)q * D + ot[t0 + t]) * D + b];
+    }
+    const double* xb = Xb + j * P;
+    if (stage_cols) {
+        if (j < ncols)
+            for (int c = 0; c < P; ++c) sc[tid * ldx + c] = xb[c];
+        xb = sc + tid * ldx;
+    }
+    __syncthreads();
+    if (j >= ncols) return;
+    const int b = ob[j];
+    for (int t = 0; t < nt; ++t) {
+        const double* xa = sx + t * P;
+        const double* bt = sb + (long long)t * QD + b;
+        double acc = 0.0;
+        for (int q = 0; q < Q; ++q) {
+            double v[4];
+            const double r = ex_dist(xa, xb, cols + q * EX_MAX_COLS);
+            ex_eval(kinds[q], prm + 4 * q, r, v);
+            acc += bt[q * D] * v[0];
+        }
+        out[(long long)(t0 + t) * ldo + j] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Fused row reduction, stage 1: for row v = blockIdx.y and chunk c = blockIdx.x of EX_RD_CHUNKS
+// equal chunks of the row, part[v][c] = (sum B[v][i] X[v][i], sum X[v][i]^2) over the chunk:
+// threads stride the chunk, then a tree over the block -- a fixed order.  block 256, LDS 512
+// doubles.  Stage 2 (k_ex_rowdot_sum): grid ceil(k / 64), block 64, a thread sums its row's
+// chunks in order.  No atomics: the same bits from call to call.
+// ---------------------------------------------------------------------------
+#define EX_RD_CHUNKS 64
+__global__ void __launch_bounds__(256)
+k_ex_rowdot_part(const double* __restrict__ B, const double* __restrict__ X, long long n,
+                 double* __restrict__ part) {
+    RL_SMEM(smem);
+    double* rd = reinterpret_cast<double*>(smem);      // [256] dots, [256] squares
+    const int tid = threadIdx.x;
+    const long long len = (n + EX_RD_CHUNKS - 1) / EX_RD_CHUNKS;
+    const long long i0 = (long long)blockIdx.x * len;
+    const long long i1 = i0 + len < n ? i0 + len : n;
+    const double* b = B + (long long)blockIdx.y * n;
+    const double* x = X + (long long)blockIdx.y * n;
+    double dot = 0.0, sq = 0.0;
+    for (long long i = i0 + tid; i < i1; i += 256) {
+        const double xi = x[i];
+        dot += b[i] * xi;
+        sq += xi * xi;
+    }
+    rd[tid] = dot;
+    rd[256 + tid] = sq;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) {
+            rd[tid] += rd[tid + w];
+            rd[256 + tid] += rd[256 + tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double* p = part + ((long long)blockIdx.y * EX_RD_CHUNKS + blockIdx.x) * 2;
+        p[0] = rd[0];
+        p[1] = rd[256];
+    }
+}
+
+__global__ void __launch_bounds__(64)
+k_ex_rowdot_sum(const double* __restrict__ part, int k, double* __restrict__ dots,
+                double* __restrict__ sqn) {
+    const int v = blockIdx.x * 64 + threadIdx.x;
+    if (v >= k) return;
+    double dot = 0.0, sq = 0.0;
+    for (int c = 0; c < EX_RD_CHUNKS; ++c) {
+        dot += part[((long long)v * EX_RD_CHUNKS + c) * 2];
+        sq += part[((long long)v * EX_RD_CHUNKS + c) * 2 + 1];
+    }
+    dots[v] = dot;
+    sqn[v] = sq;
+}
+
+// ---------------------------------------------------------------------------
 // Cholesky of the nk x nk diagonal block at (k0, k0) in one workgroup (LDS), in place (lower).
 // logd[k0 + r] = log L_rr.  The first column whose pivot is not a positive finite number goes to
 // *flag (if smaller than what is there: blocks run in order, one workgroup each); the

@@ -28,6 +28,9 @@ struct rl_exact {
     int* pair_start = nullptr;
     int ntiles = 0;
     double* gout = nullptr;         // gradient sums
+    double* xt = nullptr;           // test rows of rl_exact_cross_dev (kept between calls)
+    int* ot = nullptr;
+    size_t xt_cap = 0, ot_cap = 0;
     std::vector<int> lens, hbounds;
 };
 
@@ -169,7 +172,7 @@ extern "C" int rl_exact_destroy(rl_exact* h) {
     for (void* p : {(void*)h->A, (void*)h->X, (void*)h->out_of, (void*)h->bounds, (void*)h->kinds,
                     (void*)h->prm, (void*)h->cols, (void*)h->dslot, (void*)h->Bm, (void*)h->noise,
                     (void*)h->logd, (void*)h->scal, (void*)h->flag, (void*)h->ws, (void*)h->tiles,
-                    (void*)h->pair_start, (void*)h->gout})
+                    (void*)h->pair_start, (void*)h->gout, (void*)h->xt, (void*)h->ot})
         if (p) (void)hipFree(p);
     delete h;
     return RL_OK;
@@ -428,6 +431,93 @@ extern "C" int rl_exact_explained_variance(rl_exact* h, const double* Xtest, con
     if (h->state != EX_FACTORED)
         return fail(RL_EINVAL, "rl_exact_explained_variance: the handle holds no Cholesky factor");
     return ex_cross_rows(h, Xtest, test_lens, nullptr, nullptr, out);
+}
+
+// LDS of k_ex_cross_rows: the staged test rows may take kCrossRowLds bytes, the staged training
+// columns kCrossColLds more (beyond that a thread reads its column from global memory).
+static const size_t kCrossRowLds = 32 << 10, kCrossColLds = 16 << 10;
+
+extern "C" int rl_exact_cross_dev(rl_exact* h, const double* Xtest, const int* test_lens, int row0,
+                                  int nrows, double* out, void* stream) {
+    if (!h || !Xtest || !test_lens || !out) return fail(RL_EINVAL, "rl_exact_cross_dev: NULL argument");
+    if (h->state < EX_SET) return fail(RL_EINVAL, "rl_exact_cross_dev: no parameters (rl_exact_set)");
+    long long nt = 0;
+    for (int d = 0; d < h->D; ++d) {
+        if (test_lens[d] < 0) return fail(RL_EINVAL, "rl_exact_cross_dev: negative test length");
+        nt += test_lens[d];
+    }
+    if (nt > (1LL << 30)) return fail(RL_ELIMIT, "rl_exact_cross_dev: too many test points");
+    if (row0 < 0 || nrows < 0 || (long long)row0 + nrows > nt)
+        return fail(RL_EINVAL, "rl_exact_cross_dev: rows " + std::to_string(row0) + " .. " +
+                                   std::to_string((long long)row0 + nrows) + " of " +
+                                   std::to_string(nt) + " test points");
+    if (nrows == 0) return RL_OK;
+    const int P = h->P, Q = h->Q, D = h->D;
+    const size_t row_bytes = ((size_t)P + (size_t)Q * D) * sizeof(double);
+    if (row_bytes > kCrossRowLds)
+        return fail(RL_ELIMIT, "rl_exact_cross_dev: one test row (P + Q D = " +
+                                   std::to_string(row_bytes / 8) + " values) exceeds the kernel's LDS");
+    RL_HIP(hipSetDevice(h->device));
+    const hipStream_t st = (hipStream_t)stream;
+    // outputs of the window's rows, from the lengths
+    std::vector<int> o((size_t)nrows);
+    {
+        long long begin = 0;
+        for (int d = 0; d < D; ++d) {
+            const long long end = begin + test_lens[d];
+            const long long a = std::max<long long>(begin, row0), b = std::min<long long>(end, (long long)row0 + nrows);
+            for (long long i = a; i < b; ++i) o[(size_t)(i - row0)] = d;
+            begin = end;
+        }
+    }
+    if (h->xt_cap < (size_t)nrows * P) {
+        if (h->xt) RL_HIP(hipFree(h->xt));
+        h->xt = nullptr;
+        h->xt_cap = 0;
+        RL_HIP(hipMalloc((void**)&h->xt, (size_t)nrows * P * sizeof(double)));
+        h->xt_cap = (size_t)nrows * P;
+    }
+    if (h->ot_cap < (size_t)nrows) {
+        if (h->ot) RL_HIP(hipFree(h->ot));
+        h->ot = nullptr;
+        h->ot_cap = 0;
+        RL_HIP(hipMalloc((void**)&h->ot, (size_t)nrows * sizeof(int)));
+        h->ot_cap = (size_t)nrows;
+    }
+    // the host rows are consumed before the call returns; the kernel stays queued
+    RL_HIP(hipMemcpyAsync(h->xt, Xtest + (long long)row0 * P, (size_t)nrows * P * sizeof(double),
+                          hipMemcpyHostToDevice, st));
+    RL_HIP(hipMemcpyAsync(h->ot, o.data(), (size_t)nrows * sizeof(int), hipMemcpyHostToDevice, st));
+    RL_HIP(hipStreamSynchronize(st));
+    const int ldx = P | 1;
+    const int stage_cols = (size_t)EX_CR_COLS * ldx * sizeof(double) <= kCrossColLds ? 1 : 0;
+    const int rg = (int)std::min<size_t>({(size_t)nrows, (size_t)EX_T, kCrossRowLds / row_bytes});
+    const size_t lds = (size_t)rg * row_bytes + (stage_cols ? (size_t)EX_CR_COLS * ldx * sizeof(double) : 0);
+    const long long gx = ((long long)h->n + EX_CR_COLS - 1) / EX_CR_COLS;
+    const int gy = (nrows + rg - 1) / rg;
+    if (gy > 65535) return fail(RL_ELIMIT, "rl_exact_cross_dev: too many row groups in one call");
+    RL_LAUNCH(k_ex_cross_rows, dim3((unsigned)gx, (unsigned)gy), dim3(EX_CR_COLS), lds, st, out,
+              (long long)h->n, nrows, h->n, rg, (const double*)h->xt, (const int*)h->ot,
+              (const double*)h->X, (const int*)h->out_of, P, Q, (const int*)h->kinds,
+              (const double*)h->prm, (const int*)h->cols, (const double*)h->Bm, D, stage_cols, ldx);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+extern "C" int rl_row_dots(const double* B, const double* X, int nvec, long long n, double* dots,
+                           double* sqnorms, double* ws, void* stream) {
+    if (!B || !X || !dots || !sqnorms || !ws) return fail(RL_EINVAL, "rl_row_dots: NULL argument");
+    if (nvec < 0 || n < 1) return fail(RL_EINVAL, "rl_row_dots: bad sizes");
+    if (nvec > 65535) return fail(RL_ELIMIT, "rl_row_dots: more than 65535 rows in one call");
+    if (nvec == 0) return RL_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    RL_LAUNCH(k_ex_rowdot_part, dim3(EX_RD_CHUNKS, nvec), dim3(256), 512 * sizeof(double), st, B, X,
+              n, ws);
+    RL_HIP(hipGetLastError());
+    RL_LAUNCH(k_ex_rowdot_sum, dim3((nvec + 63) / 64), dim3(64), 0, st, (const double*)ws, nvec,
+              dots, sqnorms);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
 }
 
 extern "C" int rl_exact_invert(rl_exact* h) {

@@ -64,7 +64,8 @@ class InterpolatedLLGP:
     def __init__(self, Xs, Ys, normalize=True, lo=None, hi=None, m=None,
                  name='lmc', metrics=False, prediction='on-the-fly',
                  max_procs=None, trace_iterations=15, tolerance=1e-4,
-                 functional_kernel=None, group=None, device_index=0, device_probes=None):
+                 functional_kernel=None, group=None, device_index=0, device_probes=None,
+                 variance_batch=None):
         self.name = name
         self.input_dim, self.output_dim = self._validate_io(Xs, Ys)
         self.normalizer = None
@@ -82,6 +83,21 @@ class InterpolatedLLGP:
             raise ValueError('Variance prediction method {} unrecognized'
                              .format(prediction))
         self.prediction = prediction
+        # variance_batch: None keeps the host-assembled right-hand sides of the reference
+        # (interpolated_llgp.py:358-397); an integer >= 1 tiles 'on-the-fly' and 'precompute'
+        # on the device with that many rows per solve (approx/quadforms.py); 'exact' ignores it
+        if variance_batch is not None:
+            if (isinstance(variance_batch, bool) or not isinstance(variance_batch, (int, np.integer))
+                    or variance_batch < 1):
+                raise ValueError('variance_batch must be None or an integer >= 1, got {!r}'
+                                 .format(variance_batch))
+            variance_batch = int(variance_batch)
+        self.variance_batch = variance_batch
+        # (the residual rule of the tiled solves: Iterative.solve's default, which the host
+        # path's solves run with)
+        self.variance_tolerance = 1e-4
+        # what the last tiled variance computation returned per row (approx.quadforms.QuadForms)
+        self.variance_stats = None
         self._functional_kernel = functional_kernel
         self._functional_kernel.set_input_dim(self.input_dim)
         if any(len(ad) > 2 for ad in functional_kernel.active_dims):
@@ -344,7 +360,32 @@ class InterpolatedLLGP:
             K += Bq[np.ix_(ro, co)] * k.from_dist(dist[k.active_dims])
         return K
 
+    def _light_exact(self):
+        """The exact kernel's device handle holding the training points and the current
+        parameters: set, never assembled or factored (no n x n buffer).  Kernels without a
+        device formula raise exact_descriptors' NotImplementedError."""
+        if 'light_exact' not in self._caches:
+            from .._native import ExactOp
+            fk = self._functional_kernel
+            X = np.vstack(self.Xs)
+            op = ExactOp(X.shape[0], X.shape[1], device_index=self._device_index)
+            op.set(X, [len(x) for x in self.Xs], fk.kernels, fk.coreg_mats(), fk.noise)
+            self._caches['light_exact'] = op
+        return self._caches['light_exact']
+
+    def _var_on_the_fly_tiled(self, Xs):
+        from ..approx.quadforms import CrossRows, quad_forms
+        lens = [len(X) for X in Xs]
+        if sum(lens) == 0:
+            return np.zeros(0)
+        rows = CrossRows(self._light_exact(), np.vstack(Xs), lens)
+        self.variance_stats = quad_forms(self._K, rows, rows.total_rows, self.variance_batch,
+                                         self.variance_tolerance)
+        return self.variance_stats.v
+
     def _var_on_the_fly(self, _W, Xs):
+        if self.variance_batch is not None:
+            return self._var_on_the_fly_tiled(Xs)
         Kx = self._exact_cross_kernel(Xs)
         if Kx.shape[0] == 0:
             return np.zeros(0)
@@ -364,6 +405,13 @@ class InterpolatedLLGP:
             (ad,) = self.interpolants
             W, WT = self.interpolants[ad]
             gk = self._grid_kernels[ad]
+            if self.variance_batch is not None:
+                from ..approx.quadforms import GridColumnRows, quad_forms
+                rows = GridColumnRows(gk)
+                self.variance_stats = quad_forms(self._K, rows, rows.total_rows,
+                                                 self.variance_batch, self.variance_tolerance)
+                self._caches['nu'] = self.variance_stats.v
+                return self._caches['nu']
             Dm = W.shape[1]
             # K_XU e_i for every grid index: columns of W K_UU
             KXU = W.dot(gk.grid_K.matmat(np.identity(Dm)))          # (n, Dm)
