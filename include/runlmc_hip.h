@@ -380,6 +380,7 @@ int rl_segment_dots(const double* U, const double* V, const int* offsets, int nv
 #define RL_EXACT_RBF 0          /* exp(-g r^2 / 2)              params [g]        (kern/rbf.py) */
 #define RL_EXACT_MATERN32 1     /* (1 + s) e^-s, s = sqrt(3) g r  params [g]      (kern/matern32.py) */
 #define RL_EXACT_STDPERIODIC 2  /* exp(-g sin^2(pi r / T) / 2)  params [g, T]     (kern/std_periodic.py) */
+#define RL_EXACT_MATERN52 3     /* (1 + s + s^2 / 3) e^-s, s = sqrt(5) g r  params [g]  (no reference twin) */
 #define RL_EXACT_SCALED 16      /* OR'ed in: c k(r), params[2] = c, one more parameter (kern/scaled.py) */
 /* n data points of P input columns each. */
 int rl_exact_create(int device, int n, int P, rl_exact** out);

@@ -515,8 +515,8 @@ def exact_descriptors(kernels):
     """(kinds [Q], params [Q, 4], active columns [Q, 4], parameters per kernel) of the package's
     kernels for rl_exact_set.  A kernel class without a device formula raises
     NotImplementedError naming it: there is no host fallback."""
-    from .kern.stationary import RBF, Matern32, StdPeriodic, Scaled
-    base = {RBF: 0, Matern32: 1, StdPeriodic: 2}
+    from .kern.stationary import RBF, Matern32, Matern52, StdPeriodic, Scaled
+    base = {RBF: 0, Matern32: 1, StdPeriodic: 2, Matern52: 3}
     kinds, params, cols, nder = [], [], [], []
     for k in kernels:
         scaled = type(k) is Scaled

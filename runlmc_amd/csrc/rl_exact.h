@@ -29,6 +29,7 @@
 #define EX_RBF 0
 #define EX_MATERN32 1
 #define EX_STDPERIODIC 2
+#define EX_MATERN52 3
 #define EX_SCALED 16
 
 #if !defined(RL_EMU)
@@ -64,7 +65,16 @@ __device__ __forceinline__ int ex_eval(int kind, const double* prm, double r, do
         np = 1;
         break;
     }
-    default: {      // EX_STDPERIODIC
+    case EX_MATERN52: {
+        const double root5r = r * 2.23606797749979;
+        const double s = root5r * g;
+        const double e = exp(-s);
+        v[0] = (1.0 + s + s * s / 3.0) * e;
+        v[1] = -(root5r * s / 3.0) * (1.0 + s) * e;
+        np = 1;
+        break;
+    }
+    default: {      // EX_STDPERIODIC (rl_exact_set admits no other kind)
         const double T = prm[1];
         const double arg = 3.141592653589793 / T * r;
         const double s = sin(arg);

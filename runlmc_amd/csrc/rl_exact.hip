@@ -197,7 +197,7 @@ extern "C" int rl_exact_set(rl_exact* h, const double* X, const int* lens, int D
     std::vector<int> dslot(Q), cols((size_t)Q * EX_MAX_COLS);
     for (int q = 0; q < Q; ++q) {
         const int base = kinds[q] & ~EX_SCALED;
-        if (base != EX_RBF && base != EX_MATERN32 && base != EX_STDPERIODIC)
+        if (base != EX_RBF && base != EX_MATERN32 && base != EX_STDPERIODIC && base != EX_MATERN52)
             return fail(RL_EINVAL, "rl_exact_set: unknown kernel kind " + std::to_string(kinds[q]));
         dslot[q] = nslot;
         nslot += ex_nder(kinds[q]);

@@ -2,29 +2,40 @@
 //
 // A Toeplitz block whose first row is
 //
-//     t_i = (c0 + c1 i + c2 i^2) rho^i,      0 < rho <= 1,
+//     t_i = (c0 + c1 i + c2 i^2 + c3 i^3) rho^i,      0 < rho <= 1,
 //
 // -- the Matern-3/2 kernel (1 + a r) exp(-a r) of the reference on a regular grid
 // (runlmc/kern/matern32.py:40-42: rho = exp(-a h), c1 = a h c0), its derivative
 // with respect to the inverse length scale (-3 gamma r^2 exp(-a r),
-// matern32.py:50-55: c2 only), a plain exponential -- is EXACTLY semiseparable:
-// with the causal sums  F^k_i = sum_{j <= i} (i - j)^k rho^(i - j) x_j  and the
-// anti-causal ones  H^k_i = sum_{j >= i} (j - i)^k rho^(j - i) x_j,
+// matern32.py:50-55: c2 only), a plain exponential, the Matern-5/2 kernel
+// (1 + s + s^2 / 3) exp(-s), s = sqrt(5) gamma r (kern/stationary.py: degree 2) and ITS
+// derivative -(5 gamma r^2 / 3)(1 + s) exp(-s) (c2 and c3: the one row of degree 3) -- is
+// EXACTLY semiseparable: with the causal sums
+// F^k_i = sum_{j <= i} (i - j)^k rho^(i - j) x_j  and the anti-causal ones
+// H^k_i = sum_{j >= i} (j - i)^k rho^(j - i) x_j,
 //
-//     (T x)_i = c0 (F^0_i + H^0_i - x_i) + c1 (F^1_i + H^1_i) + c2 (F^2_i + H^2_i),
+//     (T x)_i = c0 (F^0_i + H^0_i - x_i) + sum_{k = 1..3} ck (F^k_i + H^k_i),
 //     F^0_i = rho F^0_{i-1} + x_i,   F^1_i = rho (F^1_{i-1} + F^0_{i-1}),
-//     F^2_i = rho (F^2_{i-1} + 2 F^1_{i-1} + F^0_{i-1})          (H: mirrored).
+//     F^2_i = rho (F^2_{i-1} + 2 F^1_{i-1} + F^0_{i-1}),
+//     F^3_i = rho (F^3_{i-1} + 3 F^2_{i-1} + 3 F^1_{i-1} + F^0_{i-1})      (H: mirrored)
+//
+// (the binomial expansion of (i - j)^k = ((i - 1 - j) + 1)^k).  A state carried n steps on
+// without input picks up the same binomials with powers of n (sf_carry):
+//     V^k += rho^n sum_l binom(k, l) n^(k - l) S^l.
+// NS = 2, 3 or 4 states per direction: an operator runs ALL its filter tops at the largest
+// NS any of them needs (coefficients beyond a top's degree are zero); a single-top product
+// (the gradient's dK) at the top's own.
 //
 // So  K x = sum_q B_q (x) T_q x  for such tops is a block-parallel scan that
 // reads x and writes y -- no zero-padded complex intermediates, no transform:
 //
 //   k_sf_carries2  per chunk of RL_SF_G grid points and row: the state the chunk
 //   (k_sf_carries  alone leaves at its last point (F) and at its first point (H)
-//    for three     -- 2 NS weighted sums per filter, lanes along the grid; two-state
-//    states)       filters: sums and differences of a point and its mirror halve the
+//    for three and -- 2 NS weighted sums per filter, lanes along the grid; two-state
+//    four states)  filters: sums and differences of a point and its mirror halve the
 //                  multiply-adds (round 5);
 //   k_sf_scan1     per (vector, channel, direction): the chunks' states chained
-//   (k_sf_scan     ( state' = rho^G (F0, F1 + G F0, F2 + 2 G F1 + G^2 F0) + chunk ),
+//   (k_sf_scan     ( state' = rho^G (F0, F1 + G F0, F2 + 2 G F1 + G^2 F0, ...) + chunk ),
 //    above 131 072 which gives every chunk the state it starts from; a segment's chunk
 //    points)       states read once and kept in registers for both walks (round 5);
 //   k_sf_apply     per (vector, chunk): the D rows of the chunk in LDS, rank-one
@@ -39,14 +50,16 @@
 //
 // Every factor a state is carried by ACROSS segments and chunks is a power rho^n
 // that the host computed in long double and rounded once (rho^(32 s) between
-// segments, rho^G between chunks); rho itself is multiplied in at most 32 times in a
+// segments, rho^G between chunks); the polynomial factors n, n^2, n^3 of a carry are
+// exact in fp64 (n: a multiple of 32 whose odd part stays below 2^17 on any grid that fits
+// the device); rho itself is multiplied in at most 32 times in a
 // row (inside a segment): no product of 1e5 rounded rho's ever forms, and the form
 // agrees with a long-double evaluation to a few 1e-15 of |T|_1 |x|_inf (tests; the
 // transform kernels: 1e-13).
 //
 // WHICH tops take this form is decided on the host at set time, from the top row
-// itself (rl_gridop.hip: sf_detect): the parameters are fitted from four
-// samples and the fit is accepted only if  sum_i |t_i - model_i| <= 2e-14 sum_i |t_i|
+// itself (rl_gridop.hip: sf_detect): degrees 0 .. 3 in turn, the parameters fitted from
+// degree + 2 samples, and the fit is accepted only if  sum_i |t_i - model_i| <= 2e-14 sum_i |t_i|
 // over the WHOLE row -- a bound on ||T - T_model||_1, hence on the product's
 // error for every input (no trial vectors involved).
 // Reference semantics: runlmc/linalg/bttb.py:144-148, kronecker.py:39-46.
@@ -71,7 +84,7 @@ __device__ __forceinline__ int sf_pad(int i) { return i + (i >> 5); }
 
 struct SfTop {
     double rho;       // decay per grid step
-    double c[3];      // t_i = (c0 + c1 i + c2 i^2) rho^i
+    double c[4];      // t_i = (c0 + c1 i + c2 i^2 + c3 i^3) rho^i
     double rG;        // rho^G: from chunk to chunk
     double rL;        // rho^(G * seglen): from segment to segment of k_sf_scan's chunk chain
 };
@@ -93,7 +106,12 @@ struct SfParams {
 template <int NS>
 __device__ __forceinline__ double sf_step(double (&F)[NS], double rho, double x) {
     const double tt = rho * F[0];
-    if constexpr (NS == 3) {
+    if constexpr (NS == 4) {
+        const double t1 = rho * F[1], t2 = rho * F[2];
+        F[3] = fma(rho, F[3], fma(3.0, t2 + t1, tt));
+        F[2] = t2 + fma(2.0, t1, tt);
+        F[1] = t1 + tt;
+    } else if constexpr (NS == 3) {
         const double t1 = rho * F[1];
         F[2] = fma(rho, F[2], fma(2.0, t1, tt));
         F[1] = t1 + tt;
@@ -119,7 +137,10 @@ template <int NS>
 __device__ __forceinline__ void sf_carry(double (&V)[NS], const double (&S)[NS], double r, double n) {
     V[0] = fma(r, S[0], V[0]);
     V[1] = fma(r, fma(n, S[0], S[1]), V[1]);
-    if constexpr (NS == 3) V[2] = fma(r, fma(n * n, S[0], fma(2.0 * n, S[1], S[2])), V[2]);
+    if constexpr (NS >= 3) V[2] = fma(r, fma(n * n, S[0], fma(2.0 * n, S[1], S[2])), V[2]);
+    // (n^2 and n^3 are exact in fp64: see the top comment)
+    if constexpr (NS == 4)
+        V[3] = fma(r, fma(n * n * n, S[0], fma(3.0 * (n * n), S[1], fma(3.0 * n, S[2], S[3]))), V[3]);
 }
 
 // ---------------------------------------------------------------------------
@@ -694,7 +715,7 @@ __device__ __forceinline__ double sf_row_shift(double v, double* scr) {
 // ---------------------------------------------------------------------------
 struct SfBlk {                // per filter, staged in LDS
     double rho;               // decay per grid step
-    double c[3];              // t_i = (c0 + c1 i + c2 i^2) rho^i
+    double c[4];              // t_i = (c0 + c1 i + c2 i^2 + c3 i^3) rho^i
     double p32[17];           // rho^(32 s)
 };
 #define RL_SF_BLKD ((int)(sizeof(SfBlk) / sizeof(double)))
@@ -973,6 +994,7 @@ k_sf_apply(const double* __restrict__ X, double* __restrict__ Y, int nvec, int m
            int nfac, const double* __restrict__ blob, const double* __restrict__ Cin,
            int* __restrict__ next_tile) {
     constexpr int G = RL_SF_G, PAD = RL_SF_PAD, NH = RL_SF_NH, XR = NH * D, S = RL_SF_S;
+    constexpr int B2 = NS < 4 ? 2 : 1;      // filters of a row per pass unless five fit (see above)
     RL_SMEM(smem);
     const int nchan = D * NF + nfac, nblob = sf_blob_doubles(NF, nfac, D);
     double* xs = reinterpret_cast<double*>(smem);            // [D][PAD]: x, then the rows of y
@@ -1023,7 +1045,11 @@ k_sf_apply(const double* __restrict__ X, double* __restrict__ Y, int nvec, int m
     RL_SF_STAMP(99);
     // (row, segment) tasks, one per lane: the rows of x with all their filters (in batches
     // of five (NS = 2 only: three states of five filters in both directions do not fit the
-    // registers), two or one), then the mixed rows with their one filter.  A wave without
+    // registers), two or one; NS = 4: one -- with two, k_sf_apply<4, 1> spilled 64 bytes a lane
+    // inside the recurrences, <4, 10> 240, <4, 16> 332; with one <4, 1> has 248 registers and
+    // no scratch, <4, 10> 136 bytes and <4, 16> 252 (<3, 10>: 88, <3, 16>: 188), all of it the
+    // next tile's rows and addresses, outside the recurrences: -Rpass-analysis=
+    // kernel-resource-usage and the ISA), then the mixed rows with their one filter.  A wave without
     // a live task skips the pass (the emulator's cross-lane moves are workgroup barriers:
     // there every wave runs every pass).
     for (int t0 = 0; t0 < D * 16; t0 += nthr) {
@@ -1043,16 +1069,16 @@ k_sf_apply(const double* __restrict__ X, double* __restrict__ Y, int nvec, int m
 #pragma unroll
         for (int i = 0; i < S; ++i) xv[i] = cell[i];
         for (int j = 0; j < NF;) {
-            const int b = (NS == 2 && NF - j >= 5) ? 5 : (NF - j >= 2 ? 2 : 1);
+            const int b = (NS == 2 && NF - j >= 5) ? 5 : (NF - j >= B2 ? B2 : 1);
             const double* kw = kap + j * D + a;
             const double* cin0 = cinl + (size_t)(a * NF + j) * 2 * NS;
             if (j == 0) {
                 if (NS == 2 && b == 5) sf_task<2, 5, true>(cell, xv, live, s, bl, j, kw, D, cin0, scr);
-                else if (b == 2) sf_task<NS, 2, true>(cell, xv, live, s, bl, j, kw, D, cin0, scr);
+                else if (b == 2) sf_task<NS, B2, true>(cell, xv, live, s, bl, j, kw, D, cin0, scr);
                 else sf_task<NS, 1, true>(cell, xv, live, s, bl, j, kw, D, cin0, scr);
             } else {
                 if (NS == 2 && b == 5) sf_task<2, 5, false>(cell, xv, live, s, bl, j, kw, D, cin0, scr);
-                else if (b == 2) sf_task<NS, 2, false>(cell, xv, live, s, bl, j, kw, D, cin0, scr);
+                else if (b == 2) sf_task<NS, B2, false>(cell, xv, live, s, bl, j, kw, D, cin0, scr);
                 else sf_task<NS, 1, false>(cell, xv, live, s, bl, j, kw, D, cin0, scr);
             }
             j += b;

@@ -356,6 +356,8 @@ static void set_lds_attrs() {
     (void)hipFuncSetAttribute((const void*)k_sf_apply<2, D_>,                         \
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
     (void)hipFuncSetAttribute((const void*)k_sf_apply<3, D_>,                         \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+    (void)hipFuncSetAttribute((const void*)k_sf_apply<4, D_>,                         \
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
     RL_SF_ATTR(1); RL_SF_ATTR(2); RL_SF_ATTR(3); RL_SF_ATTR(4); RL_SF_ATTR(5); RL_SF_ATTR(6);
     RL_SF_ATTR(7); RL_SF_ATTR(8); RL_SF_ATTR(9); RL_SF_ATTR(10); RL_SF_ATTR(11); RL_SF_ATTR(12);
@@ -371,6 +373,8 @@ static void set_lds_attrs() {
     (void)hipFuncSetAttribute((const void*)k_sf_carries<2>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)k_sf_carries<3>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)k_sf_carries<4>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 #endif
 }
@@ -1464,10 +1468,10 @@ static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, doub
 struct SfFit {
     int deg = 0;
     long double ah = 0.0L;          // decay per grid step: rho = exp(-ah)
-    long double c[3] = {0.0L, 0.0L, 0.0L};
+    long double c[4] = {0.0L, 0.0L, 0.0L, 0.0L};
 };
 
-// sum_i |t_i - (c0 + c1 i + c2 i^2) exp(-ah i)| <= RL_SF_TOL sum_i |t_i| ?  (long double;
+// sum_i |t_i - (c0 + c1 i + c2 i^2 + c3 i^3) exp(-ah i)| <= RL_SF_TOL sum_i |t_i| ?  (long double;
 // the power is re-anchored every 256 points; stops at the first excess, so a top
 // row of another kind costs a handful of points)
 static bool sf_check(const double* t, int m, const SfFit& f, long double tot) {
@@ -1475,7 +1479,7 @@ static bool sf_check(const double* t, int m, const SfFit& f, long double tot) {
     long double err = 0.0L, pw = 1.0L;
     for (int i = 0; i < m; ++i) {
         if ((i & 255) == 0) pw = expl(-f.ah * i);
-        const long double model = (f.c[0] + (f.c[1] + f.c[2] * i) * i) * pw;
+        const long double model = (f.c[0] + (f.c[1] + (f.c[2] + f.c[3] * i) * i) * i) * pw;
         err += fabsl((long double)t[i] - model);
         if (!(err <= budget)) return false;
         pw *= rho;
@@ -1483,13 +1487,15 @@ static bool sf_check(const double* t, int m, const SfFit& f, long double tot) {
     return true;
 }
 
-// Is the top row t_i = (c0 + c1 i + c2 i^2) rho^i?  The decimated sequence
+// Is the top row t_i = (c0 + c1 i + c2 i^2 + c3 i^3) rho^i?  The decimated sequence
 // u_k = t_{k j} of such a row satisfies  sum_l binom(p+1, l) (-R)^l u_{p+1-l} = 0
 // with R = rho^j (p: the degree) -- one polynomial equation for R from p + 2
 // samples; j is taken where the row has fallen to about 0.6 of its largest
 // entry, so that the roots are well separated.  Every root in (0, 1] is a
 // candidate; the coefficients follow from the first p + 1 samples; the
-// candidate is accepted by sf_check over the whole row.  Degrees 0, 1, 2 in turn.
+// candidate is accepted by sf_check over the whole row.  Degrees 0, 1, 2, 3 in turn
+// (a row of a lower degree is taken at that degree: its fit does not depend on the
+// degrees tried after it).
 static bool sf_detect(const double* t, int m, SfFit* fit) {
     if (m < 8) return false;
     long double tot = 0.0L;
@@ -1511,13 +1517,14 @@ static bool sf_detect(const double* t, int m, SfFit* fit) {
             below = i - imax;
             break;
         }
-    for (int deg = 0; deg <= 2; ++deg) {
+    for (int deg = 0; deg <= 3; ++deg) {
         const int span = deg + 1, jmax = (m - 1) / span;
         if (jmax < 1) continue;
         const int j = below < 0 ? jmax : std::max(1, std::min(below, jmax));
-        long double u[4] = {0.0L, 0.0L, 0.0L, 0.0L}, coef[4];
+        long double u[5] = {0.0L, 0.0L, 0.0L, 0.0L, 0.0L}, coef[5];
         for (int k = 0; k <= span; ++k) u[k] = t[(size_t)k * j];
-        static const int binom[4][4] = {{1, 0, 0, 0}, {1, 1, 0, 0}, {1, 2, 1, 0}, {1, 3, 3, 1}};
+        static const int binom[5][5] = {
+            {1, 0, 0, 0, 0}, {1, 1, 0, 0, 0}, {1, 2, 1, 0, 0}, {1, 3, 3, 1, 0}, {1, 4, 6, 4, 1}};
         for (int l = 0; l <= span; ++l) coef[l] = ((l & 1) ? -1.0L : 1.0L) * binom[span][l] * u[span - l];
         auto f = [&](long double R) {
             long double v = 0.0L;
@@ -1554,6 +1561,16 @@ static bool sf_detect(const double* t, int m, SfFit* fit) {
                 c.c[2] = (p2 - 2.0L * p1 + p0) / (2.0L * jj * jj);
                 c.c[1] = (p1 - p0) / jj - c.c[2] * jj;
             }
+            if (deg == 3) {
+                // forward differences of p(k j) at k = 0: d3 = 6 c3 j^3, d2 = 2 c2 j^2 + d3,
+                // d1 = c1 j + c2 j^2 + c3 j^3
+                const long double p3 = u[3] / (R * R * R);
+                const long double d1 = p1 - p0, d2 = p2 - 2.0L * p1 + p0,
+                                  d3 = p3 - 3.0L * p2 + 3.0L * p1 - p0;
+                c.c[3] = d3 / (6.0L * jj * jj * jj);
+                c.c[2] = (d2 - d3) / (2.0L * jj * jj);
+                c.c[1] = d1 / jj - c.c[2] * jj - c.c[3] * jj * jj;
+            }
             if (sf_check(t, m, c, tot)) {
                 *fit = c;
                 return true;
@@ -1577,14 +1594,14 @@ static void sf_parity_weights_chunk(const SfFit& f, double* out) {
 }
 static void sf_device_top(const SfFit& f, int m, SfTop* tp, SfBlk* bk, double* pw) {
     tp->rho = (double)expl(-f.ah);
-    for (int k = 0; k < 3; ++k) tp->c[k] = (double)f.c[k];
+    for (int k = 0; k < 4; ++k) tp->c[k] = (double)f.c[k];
     tp->rG = (double)expl(-f.ah * RL_SF_G);
     // k_sf_scan chains the chunks in 32 segments of seglen chunks each
     const int nchunks = (m + RL_SF_G - 1) / RL_SF_G, seglen = (nchunks + RL_SF_NSEG - 1) / RL_SF_NSEG;
     tp->rL = (double)expl(-f.ah * RL_SF_G * (long double)seglen);
     for (int j = 0; j <= RL_SF_G; ++j) pw[j] = (double)expl(-f.ah * j);
     bk->rho = tp->rho;
-    for (int k = 0; k < 3; ++k) bk->c[k] = tp->c[k];
+    for (int k = 0; k < 4; ++k) bk->c[k] = tp->c[k];
     for (int n = 0; n <= 16; ++n) bk->p32[n] = (double)expl(-f.ah * RL_SF_S * n);
 }
 
@@ -1617,9 +1634,10 @@ static int sf_reserve(rl_gridop* g, int nvec, int NF, int nfac, int NS) {
     }
     return RL_OK;
 }
-static size_t sf_apply_lds(int D, int nfac, int NF, int nthr) {
+// (NS: states per direction; two-state launches keep the three-state size)
+static size_t sf_apply_lds(int D, int nfac, int NF, int nthr, int NS) {
     size_t b = ((size_t)(D + nfac) * RL_SF_PAD + sf_blob_doubles(NF, nfac, D) +
-                (size_t)(D * NF + nfac) * 2 * 3 + 1) * sizeof(double);
+                (size_t)(D * NF + nfac) * 2 * std::max(NS, 3) + 1) * sizeof(double);
 #if defined(RL_EMU)
     b += (size_t)(nthr / 64) * 128 * sizeof(double);
 #else
@@ -1659,14 +1677,14 @@ static int sf_launch(rl_gridop* g, const SfParams& sp, const double* blob, const
 #if defined(RL_EMU)
     const int ntiles = nch * nvec, resident = 7;            // (so that tests walk several tiles)
 #else
-    const size_t tile_lds = sf_apply_lds(D, sp.nfac, sp.NF, 256);
+    const size_t tile_lds = sf_apply_lds(D, sp.nfac, sp.NF, 256, NS);
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / tile_lds));
     const int ntiles = nch * nvec, resident = per_cu * RL_LR_CUS;
 #endif
 #define RL_SF_APPLY(D_)                                                                      \
     case D_:                                                                                    \
         RL_LAUNCH((k_sf_apply<NS, D_>), dim3(std::min(ntiles, resident)), dim3(64 * waves),     \
-                  sf_apply_lds(D, sp.nfac, sp.NF, 64 * waves), st, X, Y, nvec, g->m, sp.NF,     \
+                  sf_apply_lds(D, sp.nfac, sp.NF, 64 * waves, NS), st, X, Y, nvec, g->m, sp.NF, \
                   sp.nfac, blob, (const double*)g->sf_Cin, g->sf_next);                         \
         break
     switch (D) {
@@ -1685,8 +1703,11 @@ static int sf_launch(rl_gridop* g, const SfParams& sp, const double* blob, const
 static int sf_apply_all(rl_gridop* g, const double* X, double* Y, int nvec, hipStream_t st) {
     SfParams sp{g->sf_n, g->sf_nfac, g->sf_tops, g->sf_pw, g->sf_kappa, g->sf_facA, g->sf_facAW,
                 g->sf_facJ, g->sf_pwp};
-    return g->sf_ns == 3 ? sf_launch<3>(g, sp, g->sf_blob, X, Y, nvec, st)
-                         : sf_launch<2>(g, sp, g->sf_blob, X, Y, nvec, st);
+    switch (g->sf_ns) {
+        case 4: return sf_launch<4>(g, sp, g->sf_blob, X, Y, nvec, st);
+        case 3: return sf_launch<3>(g, sp, g->sf_blob, X, Y, nvec, st);
+        default: return sf_launch<2>(g, sp, g->sf_blob, X, Y, nvec, st);
+    }
 }
 // (I_D (x) T_q) X for one filter top
 static int sf_apply_top(rl_gridop* g, int q, const double* X, double* Y, int nvec, hipStream_t st) {
@@ -1694,8 +1715,11 @@ static int sf_apply_top(rl_gridop* g, int q, const double* X, double* Y, int nve
     SfParams sp{1, 0, g->sf_tops + j, g->sf_pw + (size_t)j * (RL_SF_G + 1), g->ones, nullptr,
                 nullptr, nullptr, g->sf_pwp + (size_t)j * 2 * RL_SF_G};
     const double* blob = g->sf_blob_top + (size_t)j * sf_blob_doubles(1, 0, g->D);
-    return g->sf_top_ns[q] == 3 ? sf_launch<3>(g, sp, blob, X, Y, nvec, st)
-                                : sf_launch<2>(g, sp, blob, X, Y, nvec, st);
+    switch (g->sf_top_ns[q]) {
+        case 4: return sf_launch<4>(g, sp, blob, X, Y, nvec, st);
+        case 3: return sf_launch<3>(g, sp, blob, X, Y, nvec, st);
+        default: return sf_launch<2>(g, sp, blob, X, Y, nvec, st);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2113,7 +2137,7 @@ static int forms_setup(rl_gridop* g, const std::vector<double>& A, const std::ve
             if (sf_detect(g->h_tops.data() + (size_t)q * m, m, &fits[q])) {
                 g->top_form[q] = 2;
                 g->sf_slot[q] = nfilt++;
-                g->sf_top_ns[q] = fits[q].c[2] != 0.0L ? 3 : 2;
+                g->sf_top_ns[q] = fits[q].c[3] != 0.0L ? 4 : (fits[q].c[2] != 0.0L ? 3 : 2);
             }
     g->sf_n = nfilt;
     // 2. polynomial verification of the others (device; skipped while backing off
@@ -2297,8 +2321,8 @@ static int forms_setup(rl_gridop* g, const std::vector<double>& A, const std::ve
     }
     // the filter part's tile (D + nfac rows of RL_SF_PAD doubles) has to fit LDS
     // (and its incoming states four registers of each of 256 threads)
-    g->st_ok = nfilt > 0 && sf_apply_lds(D, g->sf_nfac, nfilt, 512) <= kLdsHard &&
-               (D * nfilt + g->sf_nfac) * 2 * 3 <= 4 * 256;
+    g->st_ok = nfilt > 0 && sf_apply_lds(D, g->sf_nfac, nfilt, 512, g->sf_ns) <= kLdsHard &&
+               (D * nfilt + g->sf_nfac) * 2 * std::max(g->sf_ns, 3) <= 4 * 256;
     // (few outputs, a rank-48 polynomial part AND a filter part: the transform kernels are
     // level or ahead -- measured at D = 4, Q = 3, m = 5000, 1024 vectors: 0.36 against 0.33 ms;
     // at D = 10 the two parts together take 1.65 against 2.7 ms)

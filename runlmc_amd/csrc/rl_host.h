@@ -216,9 +216,9 @@ struct rl_gridop {
     bool sf_try = false;        // eligible for the filter form: 1-D grid, not switched off
     int sf_n = 0;               // filter tops
     int sf_nfac = 0;            // rank-one factors that belong to them
-    int sf_ns = 2;              // states per direction the operator's filters need (2 or 3)
+    int sf_ns = 2;              // states per direction the operator's filters need (2, 3 or 4)
     std::vector<int> sf_slot;   // per top: its place among the filter tops, or -1
-    std::vector<int> sf_top_ns; // per top: 2 or 3
+    std::vector<int> sf_top_ns; // per top: 2, 3 or 4
     SfTop* sf_tops = nullptr;   // dev [max_tops]
     double* sf_pwp = nullptr;   // dev [max_tops][2 G]: the chunk states' parity weights (k_sf_carries2)
     double* sf_blob = nullptr;  // dev: the filter part's block for k_sf_apply (rl_filter.h)

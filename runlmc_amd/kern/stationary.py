@@ -76,6 +76,32 @@ class Matern32(StationaryKern):
         self.inv_lengthscale = float(p[0])
 
 
+class Matern52(StationaryKern):
+    """(1 + s + s^2 / 3) exp(-s), s = sqrt(5) gamma r: the file's parameter convention
+    (Matern32: s = sqrt(3) gamma r); the reference has no such kernel."""
+
+    def __init__(self, inv_lengthscale=1, name='matern52', active_dims=None):
+        super().__init__(name, active_dims)
+        self.inv_lengthscale = float(inv_lengthscale)
+
+    def from_dist(self, dists):
+        s = dists * np.sqrt(5) * self.inv_lengthscale
+        return (1 + s + s * s / 3) * np.exp(-s)
+
+    def kernel_gradient(self, dists):
+        # dk/dgamma = -(5 gamma r^2 / 3) (1 + s) exp(-s): one product, nothing cancels at r = 0
+        root5r = dists * np.sqrt(5)
+        s = root5r * self.inv_lengthscale
+        return [-(root5r * s / 3) * (1 + s) * np.exp(-s)]
+
+    @property
+    def param_array(self):
+        return np.array([self.inv_lengthscale])
+
+    def set_params(self, p):
+        self.inv_lengthscale = float(p[0])
+
+
 class StdPeriodic(StationaryKern):
     """exp(-gamma sin^2(pi r / T) / 2) (reference std_periodic.py:44-67)."""
 

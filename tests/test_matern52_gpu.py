@@ -1,0 +1,65 @@
+"""GPU run of the Matern-5/2 checks (tests/matern52_suite.py) on librunlmc_hip.so: the DPP chains
+of k_sf_apply<4, D>, the wave sums of k_sf_carries<4>, k_sf_scan1<4> / k_sf_scan<4>, the exact
+likelihood's device formula and the model on the device."""
+import pytest
+
+import matern52_suite as ms
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module', autouse=True)
+def hip_library():
+    from runlmc_amd import _lib
+    _lib.use_library(None)
+    lib = _lib.get_library()
+    assert lib.is_hip, 'GPU tests must run against librunlmc_hip.so'
+    return lib
+
+
+def test_kernel_class():
+    ms.check_kernel_class()
+
+
+@pytest.mark.parametrize('m', [601, 700, 2500])
+@pytest.mark.parametrize('gamma', [1.0, 3.0, 10.0])
+def test_detection(m, gamma):
+    ms.check_detection(m, gamma)
+
+
+@pytest.mark.parametrize('D,Q,m,k', ms.SHAPES)
+def test_four_state_products(D, Q, m, k):
+    ms.check_four_state(D, Q, m, k)
+
+
+def test_four_state_products_scan2():
+    ms.check_four_state(2, 2, 20011, 2, scan2=True)
+
+
+@pytest.mark.parametrize('n,D', [(n, D) for n in (17, 65, 200) for D in (1, 3)])
+def test_exact(n, D):
+    ms.check_exact(n, D)
+
+
+def test_exact_2d_inputs():
+    ms.check_exact(65, 3, P=2)
+
+
+def test_exact_unknown_kind():
+    ms.check_exact_unknown_kind()
+
+
+def test_model_metrics():
+    ms.check_model_metrics()
+
+
+def test_model_exact_prediction():
+    ms.check_model_exact_prediction()
+
+
+def test_model_tiled_variances():
+    ms.check_model_tiled_variances()
+
+
+def test_model_solve():
+    ms.check_model_solve()
