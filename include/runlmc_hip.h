@@ -42,11 +42,12 @@ typedef struct rl_exact rl_exact;
  * rl_solve_direct, rl_solve_pcg, rl_ski_project,
  * rl_gridop_project, rl_gridop_set_rank_hint, rl_gridop_poly_coeffs, rl_slq_log_quadrature,
  * rl_probes_to_int8 added, round 6; 5: the rl_exact_* handle of the exact likelihood; 6: rl_exact_cross_dev
- * and rl_row_dots, the tiled predictive variances; callers
+ * and rl_row_dots, the tiled predictive variances; 7: rl_sampler_*, rl_normal_fill and
+ * rl_pathwise_residual, the function draws; callers
  * built against an older version must be rebuilt).  A binding
  * compares rl_abi_version() with the RL_ABI_VERSION it was written against before its
  * first call (runlmc_amd/_lib.py does) instead of finding out through shifted arguments. */
-#define RL_ABI_VERSION 6
+#define RL_ABI_VERSION 7
 int rl_abi_version(void);
 
 const char* rl_last_error(void);
@@ -440,6 +441,80 @@ int rl_exact_invert(rl_exact* h);
  * alpha dev [n] (= K^-1 y); out host [S D^2 + D].  Inverts first if needed.  Bit-identical from
  * call to call (fixed reduction order).  dL/dtheta = 1/2 sum_ab dB[a, b] out[s][a][b].           */
 int rl_exact_grad_sums(rl_exact* h, const double* alpha, double* out);
+
+/* ---- function draws (pathwise sampling) -------------------------------------
+ * No reference twin: the reference predicts means and marginal variances only
+ * (models/interpolated_llgp.py:293-397).  A draw of the grid prior
+ *     u ~ N(0, K_UU),   K_UU = sum_q B_q (x) T_q,   B_q = A_q^T A_q + diag(kappa_q)
+ * is  u = sum_q (F_q (x) S_q) z_q  with white noise z_q, the D x C_q "channel" matrix
+ * F_q = [A_q^T, diag sqrt(kappa_q)] (F_q F_q^T = B_q; no factorisation of B_q, exact for
+ * R_q = 0 and singular B_q) and S_q S_q^T = T_q in one of two forms per top row:
+ *   form 0, circulant embedding of the EXTENDED row: the kernel itself evaluated at lags
+ *     0 .. Ls/2 (1-D) or on the (N1s/2 + 1) x (N2s/2 + 1) lag lattice (2-D), mirrored to a
+ *     circulant of length Ls (N1s x N2s), whose real spectrum lambda is clipped at zero.  One
+ *     complex inverse transform makes TWO independent draws: with xi = z_{2p} + i z_{2p+1},
+ *         Y_a(w) = sum_q sqrt(lambda_q(w) / Ls) sum_c F_q[a][c] xi_{q,c}(w),
+ *         y = sum_w Y(w) exp(+2 pi i w x / Ls)  cropped to the grid,
+ *     Re y is draw 2p and Im y draw 2p + 1 (w = w1 * N2s + w2 and Ls -> N1s N2s on 2-D grids).
+ *   form 1, polynomial rows (1-D grids; rl_gridop_top_forms reports 1): S_q = Phi_r G_q with
+ *     G_q G_q^T = C_q clipped at zero (the caller's eigendecomposition of rl_gridop_poly_coeffs'
+ *     C_q, r <= 48), r reals of noise per channel and draw.
+ * Noise layout: one draw's noise is zlen doubles: the rows q = 0 .. Q-1 one after another,
+ * row q holding C_q channels of len_q values each (channel-major: offset c * len_q + w), len_q =
+ * Ls (N1s * N2s) for form 0 and r for form 1.  The noise of draw s for a form-0 row is used
+ * together with its pair partner's (s ^ 1), so Z always holds 2 ceil(nsamp / 2) rows, a
+ * trailing odd draw's partner included.
+ * The sampler's lengths are its own (not the product handle's L): an embedding that clips
+ * nothing often needs a multiple of 2m.  Allowed lengths are odd * 2^k, odd in
+ * {1, 3, 5, 9, 15, 25}, k >= 1, at most 2^22 (at most 2048 per axis of a 2-D grid; RL_ELIMIT
+ * beyond); rl_sampler_length gives the smallest one >= want.
+ * Up to RL_SAMPLER_LDS_MAX points the transform of a 1-D pair runs inside one launch
+ * (k_smp_embed1, the transform in LDS); longer ones and 2-D grids in two (k_smp_cols: scale,
+ * mix and the first pass; k_smp_rows: the second pass and the crop; csrc/rl_sample.h).      */
+typedef struct rl_sampler rl_sampler;
+#define RL_SAMPLER_LDS_MAX 2048
+int rl_sampler_length(long long want, int* length);
+/* Borrows the grid handle as rl_ski_create does (D, the grid's shape, the polynomial basis):
+ * destroy the sampler BEFORE its grid operator.                                             */
+int rl_sampler_create(rl_gridop* g, rl_sampler** out);
+int rl_sampler_destroy(rl_sampler* h);
+/* Parameters of the draws (per parameter update of the model):
+ *   nchan     host [Q]            C_q >= 1
+ *   F         host                the Q blocks [D][C_q] one after another
+ *   forms     host [Q]            0 / 1 as above
+ *   N1s, N2s  the embedding: 1-D grids N1s = Ls, N2s = 0; 2-D grids one length per axis
+ *             (ignored when no row has form 0); N_k / 2 >= m_k - 1
+ *   ext_rows  host                for every form-0 row in order its N1s/2 + 1 kernel values
+ *                                 (2-D: [(N1s/2 + 1)][(N2s/2 + 1)])
+ *   poly_rank, poly_sqrt  host    for every form-1 row in order G_q, [r][r] row-major, r =
+ *                                 poly_rank = the rank rl_gridop_poly_coeffs reported
+ *   clipped   host [Q] out        sum |lambda_-| / sum |lambda| of every form-0 row (0 for
+ *                                 form 1: the caller knows what it clipped); may be NULL
+ *   zlen      out                 doubles of noise per draw
+ * The host computes the spectra (a mixed-radix transform, O(Ls log Ls)).  Form 1 reads the
+ * grid handle's basis: the grid's parameters must be those poly_sqrt was derived from.       */
+int rl_sampler_set(rl_sampler* h, int Q, const int* nchan, const double* F, const int* forms,
+                   int N1s, int N2s, const double* ext_rows, int poly_rank,
+                   const double* poly_sqrt, double* clipped, long long* zlen);
+/* The clipped spectrum lambda_+ the draws of form-0 row q use, natural frequency order, host
+ * out [Ls] ([N1s][N2s]) (test hook, as rl_gridop_spectrum_host; RL_EINVAL for a form-1 row).  */
+int rl_sampler_spectrum_host(const rl_sampler* h, int q, double* out);
+/* U[s] = one draw of N(0, K_UU) from the noise rows Z: Z dev [2 ceil(nsamp / 2)][zlen],
+ * U dev [nsamp][D*m].  Linear in Z; queued on `stream`.                                     */
+int rl_sampler_draw(rl_sampler* h, const double* Z, double* U, int nsamp, void* stream);
+/* Standard normal noise from a counter-based generator (splitmix64 mixing, Box-Muller in
+ * fp64): Z[i][j], i < ndraws, j < zlen, is a function of (seed, draw0 + i, j) ONLY, so a draw
+ * does not depend on how draws are tiled or how many are asked for.  Z dev [ndraws][zlen].
+ * Queued on `stream` of the CURRENT device (no handle names one, as rl_row_dots): a process
+ * with several devices selects Z's device before the call.                                   */
+int rl_normal_fill(unsigned long long seed, long long draw0, int ndraws, long long zlen,
+                   double* Z, void* stream);
+/* R[s][i] = y[i] - WU[s][i] - sqrt_eps_rows[i] * E[s][i]: the right-hand sides of Matheron's
+ * rule (y dev [n], sqrt_eps_rows dev [n]: sqrt of the noise of each data row; WU, E, R dev
+ * [nsamp][n]; R may alias WU or E).  Queued on `stream` of the current device, as above.      */
+int rl_pathwise_residual(const double* y, const double* WU, const double* E,
+                         const double* sqrt_eps_rows, double* R, int nsamp, long long n,
+                         void* stream);
 
 #ifdef __cplusplus
 }

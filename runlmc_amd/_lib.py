@@ -79,8 +79,17 @@ _SIGNATURES = {
     'rl_exact_dense_host': [_vp, _vp],
     'rl_exact_invert': [_vp],
     'rl_exact_grad_sums': [_vp, _vp, _vp],
+    'rl_sampler_length': [ctypes.c_longlong, _c_int_p],
+    'rl_sampler_create': [_vp, ctypes.POINTER(_vp)],
+    'rl_sampler_destroy': [_vp],
+    'rl_sampler_set': [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp,
+                       ctypes.POINTER(ctypes.c_longlong)],
+    'rl_sampler_spectrum_host': [_vp, _i, _vp],
+    'rl_sampler_draw': [_vp, _vp, _vp, _i, _vp],
+    'rl_normal_fill': [ctypes.c_ulonglong, ctypes.c_longlong, _i, ctypes.c_longlong, _vp, _vp],
+    'rl_pathwise_residual': [_vp, _vp, _vp, _vp, _vp, _i, ctypes.c_longlong, _vp],
 }
-ABI_VERSION = 6      # include/runlmc_hip.h: RL_ABI_VERSION
+ABI_VERSION = 7      # include/runlmc_hip.h: RL_ABI_VERSION
 _RESTYPE = {'rl_last_error': ctypes.c_char_p, 'rl_backend': ctypes.c_char_p}
 
 

@@ -668,3 +668,114 @@ class ExactOp:
         out = np.zeros(ns * D * D + D)
         self.lib.call('rl_exact_grad_sums', self._h, dev_ptr(a), host_ptr(out))
         return out[:ns * D * D].reshape(ns, D, D), out[ns * D * D:].copy()
+
+
+# -- function draws (include/runlmc_hip.h: rl_sampler_*) -------------------------------------------
+def sampler_length(lib, want):
+    """The smallest embedding length the sampler allows that is >= want (rl_sampler_length)."""
+    out = ctypes.c_int()
+    lib.call('rl_sampler_length', int(want), ctypes.byref(out))
+    return out.value
+
+
+def normal_fill(lib, seed, draw0, ndraws, zlen, device, out=None):
+    """(ndraws, zlen) tensor of standard normals: element (i, j) is a function of
+    (seed, draw0 + i, j) only (rl_normal_fill)."""
+    ndraws, zlen = int(ndraws), int(zlen)
+    if out is None:
+        out = torch.empty((ndraws, zlen), dtype=torch.float64, device=device)
+    elif tuple(out.shape) != (ndraws, zlen) or out.dtype != torch.float64:
+        raise ValueError('out must be a float64 tensor of shape (%d, %d)' % (ndraws, zlen))
+    lib.call('rl_normal_fill', int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0), ndraws, zlen,
+             dev_ptr(out), lib.stream_ptr(out.device))
+    return out
+
+
+def pathwise_residual(lib, y, WU, E, sqrt_eps_rows):
+    """R[s] = y - WU[s] - sqrt_eps_rows * E[s] on the device (rl_pathwise_residual)."""
+    k, n = WU.shape
+    if tuple(E.shape) != (k, n) or y.shape[0] != n or sqrt_eps_rows.shape[0] != n:
+        raise ValueError('shapes of y, WU, E and sqrt_eps_rows do not match')
+    R = torch.empty_like(WU)
+    lib.call('rl_pathwise_residual', dev_ptr(y), dev_ptr(WU.contiguous()), dev_ptr(E.contiguous()),
+             dev_ptr(sqrt_eps_rows), dev_ptr(R), k, n, lib.stream_ptr(WU.device))
+    return R
+
+
+class Sampler:
+    """Device handle of the prior draws u ~ N(0, K_UU) of a grid operator (rl_sampler_*)."""
+
+    def __init__(self, gridop):
+        self.lib = gridop.lib
+        self.grid = gridop                  # kept alive: the handle borrows it
+        self.device = gridop.device
+        self._h = ctypes.c_void_p()
+        self.lib.call('rl_sampler_create', gridop.handle, ctypes.byref(self._h))
+        self.zlen = 0
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h is not None and h.value:
+            self.lib.cdll.rl_sampler_destroy(h)
+            self._h = ctypes.c_void_p()
+
+    @property
+    def handle(self):
+        return self._h
+
+    def set(self, channels, forms, lengths=None, ext_rows=None, poly_rank=0, poly_sqrt=None):
+        """channels[q]: F_q (D, C_q); forms[q]: 0 embedding / 1 polynomial; lengths: (Ls,) or
+        (N1s, N2s); ext_rows: one array per embedding row; poly_sqrt: one (r, r) array per
+        polynomial row.  Returns clipped (Q,) and sets .zlen."""
+        Q = len(channels)
+        if len(forms) != Q:
+            raise ValueError('need one form per row')
+        D = self.grid.D
+        Fs = [as_f64(f) for f in channels]
+        for f in Fs:
+            if f.ndim != 2 or f.shape[0] != D or f.shape[1] < 1:
+                raise ValueError('channel matrices must be (%d, C) with C >= 1' % D)
+        nchan = np.ascontiguousarray([f.shape[1] for f in Fs], dtype=np.int32)
+        F = np.ascontiguousarray(np.concatenate([f.reshape(-1) for f in Fs]))
+        forms = np.ascontiguousarray(forms, dtype=np.int32)
+        lengths = tuple(int(v) for v in (lengths or ()))
+        N1s = lengths[0] if lengths else 0
+        N2s = lengths[1] if len(lengths) > 1 else 0
+        ext = (np.ascontiguousarray(np.concatenate([as_f64(r).reshape(-1) for r in ext_rows]))
+               if ext_rows else None)
+        if ext is not None:
+            per = (N1s // 2 + 1) * ((N2s // 2 + 1) if N2s else 1)
+            if ext.size != per * int((forms == 0).sum()):
+                raise ValueError('ext_rows must hold %d values per embedding row' % per)
+        sq = None
+        if poly_sqrt:
+            sq = np.ascontiguousarray(np.stack([as_f64(g) for g in poly_sqrt]))
+            if sq.shape != (int((forms == 1).sum()), int(poly_rank), int(poly_rank)):
+                raise ValueError('poly_sqrt must hold one (r, r) matrix per polynomial row')
+        clipped = np.zeros(Q)
+        zlen = ctypes.c_longlong()
+        self.lib.call('rl_sampler_set', self._h, Q, host_ptr(nchan), host_ptr(F), host_ptr(forms),
+                      N1s, N2s, host_ptr(ext), int(poly_rank), host_ptr(sq), host_ptr(clipped),
+                      ctypes.byref(zlen))
+        self.zlen = int(zlen.value)
+        return clipped
+
+    def spectrum(self, q, length):
+        """The clipped spectrum of embedding row q (`length` values, natural order): test hook."""
+        out = np.empty(int(length))
+        self.lib.call('rl_sampler_spectrum_host', self._h, int(q), host_ptr(out))
+        return out
+
+    def draw(self, Z, nsamp=None):
+        """Z: (2 ceil(nsamp / 2), zlen) noise on the device -> (nsamp, D * m) draws."""
+        rows = Z.shape[0]
+        nsamp = rows if nsamp is None else int(nsamp)
+        if Z.dtype != torch.float64 or Z.dim() != 2 or Z.shape[1] != self.zlen:
+            raise ValueError('noise must be a float64 tensor of %d columns' % self.zlen)
+        if nsamp < 0 or rows != 2 * ((nsamp + 1) // 2):
+            raise ValueError('%d draws need %d rows of noise, got %d'
+                             % (nsamp, 2 * ((nsamp + 1) // 2), rows))
+        U = torch.empty((nsamp, self.grid.width), dtype=torch.float64, device=self.device)
+        self.lib.call('rl_sampler_draw', self._h, dev_ptr(Z.contiguous()), dev_ptr(U), nsamp,
+                      self.lib.stream_ptr(self.device))
+        return U

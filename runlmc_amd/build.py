@@ -15,10 +15,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
-# four translation units (rl_host.h holds what they share); runlmc_hip.hip includes all of them
+# five translation units (rl_host.h holds what they share); runlmc_hip.hip includes all of them
 # (experiment builds that need one code object)
 SOURCES = [os.path.join(CSRC, n) for n in ('rl_gridop.hip', 'rl_ski.hip', 'rl_solve.hip',
-                                            'rl_exact.hip')]
+                                            'rl_exact.hip', 'rl_sample.hip')]
 UNITY = os.path.join(CSRC, 'runlmc_hip.hip')
 import glob
 HEADERS = sorted(glob.glob(os.path.join(CSRC, '*.h'))) + [

@@ -29,6 +29,7 @@ import logging
 
 import numpy as np
 import scipy.spatial.distance as sdist
+import torch
 
 from ..approx.interpolation import autogrid, multi_interpolant
 from ..approx.iterative import Iterative
@@ -452,6 +453,87 @@ class InterpolatedLLGP:
             mu = [m * sd + mean for m, (mean, sd) in zip(mu, self.normalizer)]
             var = [v * sd ** 2 for v, (_, sd) in zip(var, self.normalizer)]
         return mu, var
+
+    # -- function draws (no reference twin; approx/pathwise.py) -------------------------------
+    def _pathwise_samplers(self, max_embed):
+        """One GridSampler per term of the operator, in its term order, for the current
+        parameters (rebuilt after parameters_changed)."""
+        from ..approx.pathwise import GridSampler
+        key = ('samplers', int(max_embed))
+        if key not in self._caches:
+            fk = self._functional_kernel
+            out = []
+            for ad, gk in self._grid_kernels.items():
+                kidx = fk.active_dims[ad]
+                out.append(GridSampler(gk, [fk.kernels[q] for q in kidx],
+                                       [fk.coreg_vecs[q] for q in kidx],
+                                       [fk.coreg_diags[q] for q in kidx],
+                                       self.grid_axes[ad], max_embed=max_embed))
+            self._caches[key] = out
+        return self._caches[key]
+
+    def _draw_tiles(self, size, seed, batch, max_embed, tolerance, posterior):
+        from ..approx import pathwise as pw
+        self._ensure()
+        if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 1:
+            raise ValueError('size must be an integer >= 1, got {!r}'.format(size))
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or batch < 1:
+            raise ValueError('batch must be an integer >= 1, got {!r}'.format(batch))
+        size = int(size)
+        tile = int(batch) + int(batch) % 2         # pairs of draws share a transform
+        samplers = self._pathwise_samplers(max_embed)
+        ads = list(self._grid_kernels)
+        K = self._K
+        lib, dev = K.device_operator().lib, K.device
+        tol = self._deriv_service._tol if tolerance is None else float(tolerance)
+        y = torch.from_numpy(np.ascontiguousarray(self.y, dtype=np.float64)).to(dev) if posterior else None
+        host = {ad: np.empty((size, s.grid.width)) for ad, s in zip(ads, samplers)}
+        info = []
+        for s0 in range(0, size, tile):
+            k = min(tile, size - s0)
+            Zs = [s.noise(pw.stream_seed(seed, pw.STREAM_TERM0 + t), s0, k)
+                  for t, s in enumerate(samplers)]
+            if posterior:
+                E = pw.normal_fill(lib, pw.stream_seed(seed, pw.STREAM_E), s0, k, len(self.y), dev)
+                res = pw.posterior_grid_draws(K, samplers, y, Zs, E, tol=tol)
+                U = res.draws
+                info.append(res._replace(draws=None))
+            else:
+                U = pw.prior_grid_draws(samplers, Zs, k)
+            for ad, u in zip(ads, U):
+                host[ad][s0:s0 + k] = u.cpu().numpy()
+        return pw.PathwiseDraws(self, host, seed, info)
+
+    def prior_draws(self, size, seed=0, batch=16, max_embed=16):
+        """`size` functions from the SKI model's PRIOR f = sum_t W_t u_t, u_t ~ N(0, K_t), as a
+        PathwiseDraws: call it with test inputs.  See posterior_draws for the arguments."""
+        return self._draw_tiles(size, seed, batch, max_embed, None, posterior=False)
+
+    def posterior_draws(self, size, seed=0, batch=16, tolerance=None, max_embed=16):
+        """`size` functions from the SKI model's POSTERIOR given the training data, by Matheron's
+        rule (approx/pathwise.py): prior draws on the grids, one batched solve of the operator
+        per tile of `batch` draws (rounded up to an even number: two draws share one complex
+        transform) and a back-projection.  Returns a PathwiseDraws: ``draws(Xs, noise=False)``
+        gives one (size, len(Xs[d])) array per output, de-normalised, the SAME functions at
+        whatever inputs it is asked for; ``.info`` holds solver, iterations, largest residual
+        and exit codes per tile; a residual above the tolerance is logged, not raised.
+
+        tolerance=None: the model's solve tolerance.  Draw s is a function of (seed, s) only:
+        not of size, of batch, or of the rank that draws it (every rank given the same seed
+        holds the same draws; nothing is communicated).  max_embed bounds the circulant
+        embedding (approx.pathwise.GridSampler).
+
+        The draws' mean is the mean ``predict`` returns (up to the solve tolerance).  Their
+        covariance is the SKI model's, W*(K_UU - K_UU W^T K~^-1 W K_UU)W*^T, which differs
+        slightly from ``predict``'s variances: those take the exact k(0) for the native term,
+        and 'on-the-fly' the exact cross-kernel."""
+        return self._draw_tiles(size, seed, batch, max_embed, tolerance, posterior=True)
+
+    def posterior_samples(self, Xs, size=1, seed=0, noise=False, **kw):
+        """posterior_draws(size, seed, **kw)(Xs, noise) in one call."""
+        if len(Xs) != self.output_dim:
+            raise ValueError('need one (possibly empty) input array per output')
+        return self.posterior_draws(size, seed=seed, **kw)(Xs, noise=noise)
 
     def predict_quantiles(self, Xs, quantiles=(2.5, 97.5)):
         """Gaussian predictive quantiles (multigp.py:152-174)."""
