@@ -43,11 +43,12 @@ typedef struct rl_exact rl_exact;
  * rl_gridop_project, rl_gridop_set_rank_hint, rl_gridop_poly_coeffs, rl_slq_log_quadrature,
  * rl_probes_to_int8 added, round 6; 5: the rl_exact_* handle of the exact likelihood; 6: rl_exact_cross_dev
  * and rl_row_dots, the tiled predictive variances; 7: rl_sampler_*, rl_normal_fill and
- * rl_pathwise_residual, the function draws; callers
+ * rl_pathwise_residual, the function draws; 8: rl_ski_inverse_diag, rl_ski_precond_apply,
+ * rl_diag_accumulate and rl_loo_reduce, leave-one-out cross-validation; callers
  * built against an older version must be rebuilt).  A binding
  * compares rl_abi_version() with the RL_ABI_VERSION it was written against before its
  * first call (runlmc_amd/_lib.py does) instead of finding out through shifted arguments. */
-#define RL_ABI_VERSION 7
+#define RL_ABI_VERSION 8
 int rl_abi_version(void);
 
 const char* rl_last_error(void);
@@ -515,6 +516,39 @@ int rl_normal_fill(unsigned long long seed, long long draw0, int ndraws, long lo
 int rl_pathwise_residual(const double* y, const double* WU, const double* E,
                          const double* sqrt_eps_rows, double* R, int nsamp, long long n,
                          void* stream);
+
+/* ---- Leave-one-out cross-validation (csrc/rl_loo.h; no reference twin) -------------------------
+ * With alpha = K~^-1 y and d = diag(K~^-1), observation i predicted from all the others has mean
+ * y_i - alpha_i / d_i and variance 1 / d_i (Rasmussen & Williams 5.4.2).
+ *
+ * rl_ski_inverse_diag: out dev [n], caller's row order = the diagonal of the inverse of the matrix
+ *   rl_ski_factor factorised, in ONE pass over the table of F (k_dz_diag) and no solve:
+ *   *exact = 1: diag(K~^-1) (*available = 1); *exact = 0: diag(P^-1) of the preconditioner
+ *   (*available = 2).  Rebuilds the factorisation after parameter / noise updates first.
+ *   RL_ELIMIT with the reason in rl_last_error() when *available is 0, or 3 (the 96-function basis
+ *   keeps its map in blocks).  Queued on `stream`.
+ * rl_ski_precond_apply: X = P^-1 B, ONE application of the factorisation (what rl_solve_pcg applies
+ *   every iteration; K~^-1 B to roundoff when *available = 1).  B, X dev [nvec][n], caller's row
+ *   order, not aliased.  *available 1, 2 and 3; RL_ELIMIT for 0.
+ * rl_diag_accumulate: with t = Z[v][i] (X[v][i] - C[v][i]), v ascending:  sum[i] += t,
+ *   sumsq[i] += t^2  (Z, X, C dev [nvec][n]; C may be NULL = 0; sum, sumsq dev [n], distinct).
+ *   Every entry's order over v is fixed, so probes accumulated in tiles of any size give the same
+ *   bits.  Queued on `stream` of the current device, as rl_row_dots.
+ * rl_loo_reduce: mean = y - alpha / d, var = 1 / d (dev [n]) and the log densities
+ *   -log(2 pi var) / 2 - (y - mean)^2 / (2 var) - logscale[i]  (logscale dev [n] or NULL = 0) summed
+ *   per block in a fixed order: logp_partials dev [2][RL_LOO_PARTIALS], [0][b] block b's sum over
+ *   its valid rows, [1][b] its count of rows whose d is not a positive finite number (those rows
+ *   get mean = var = NaN and stay out of the sum: reported, not clamped); *nblk = blocks used.  The
+ *   caller adds the *nblk partial sums in order.  Outputs may not alias inputs or each other.
+ *   Queued on `stream` of the current device.                                                   */
+#define RL_LOO_PARTIALS 256
+int rl_ski_inverse_diag(rl_ski* s, double* out, int* exact, void* stream);
+int rl_ski_precond_apply(rl_ski* s, const double* B, double* X, int nvec, void* stream);
+int rl_diag_accumulate(const double* Z, const double* X, const double* C, int nvec, long long n,
+                       double* sum, double* sumsq, void* stream);
+int rl_loo_reduce(const double* y, const double* alpha, const double* dinv, const double* logscale,
+                  long long n, double* mean, double* var, double* logp_partials, int* nblk,
+                  void* stream);
 
 #ifdef __cplusplus
 }

@@ -88,8 +88,12 @@ _SIGNATURES = {
     'rl_sampler_draw': [_vp, _vp, _vp, _i, _vp],
     'rl_normal_fill': [ctypes.c_ulonglong, ctypes.c_longlong, _i, ctypes.c_longlong, _vp, _vp],
     'rl_pathwise_residual': [_vp, _vp, _vp, _vp, _vp, _i, ctypes.c_longlong, _vp],
+    'rl_ski_inverse_diag': [_vp, _vp, _c_int_p, _vp],
+    'rl_ski_precond_apply': [_vp, _vp, _vp, _i, _vp],
+    'rl_diag_accumulate': [_vp, _vp, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp],
+    'rl_loo_reduce': [_vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _c_int_p, _vp],
 }
-ABI_VERSION = 7      # include/runlmc_hip.h: RL_ABI_VERSION
+ABI_VERSION = 8     # include/runlmc_hip.h: RL_ABI_VERSION
 _RESTYPE = {'rl_last_error': ctypes.c_char_p, 'rl_backend': ctypes.c_char_p}
 
 

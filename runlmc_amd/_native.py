@@ -302,6 +302,28 @@ class SkiOp:
                       ctypes.byref(ld), self.lib.stream_ptr(self.device))
         return out, float(ld.value)
 
+    def inverse_diag(self):
+        """(d, exact): the diagonal of the inverse of the matrix the factorisation inverts, a
+        device tensor (n,) in the caller's row order, from one pass over the table of F
+        (rl_ski_inverse_diag) -- diag(K~^-1) when exact, diag(P^-1) of the preconditioner when
+        not.  NotImplementedError, with the handle's reason, where there is no such diagonal."""
+        out = torch.empty((self.n,), dtype=torch.float64, device=self.device)
+        exact = ctypes.c_int()
+        self.lib.call('rl_ski_inverse_diag', self._h, dev_ptr(out), ctypes.byref(exact),
+                      self.lib.stream_ptr(self.device))
+        return out, bool(exact.value)
+
+    def precond_apply(self, B):
+        """P^-1 B: one application of the operator's factorisation to the rows of B, a (k, n)
+        device tensor in the caller's row order (rl_ski_precond_apply)."""
+        if B.dim() != 2 or B.shape[1] != self.n:
+            raise ValueError('expected rows of length %d, got shape %s' % (self.n, tuple(B.shape)))
+        B = B.contiguous()
+        out = torch.empty_like(B)
+        self.lib.call('rl_ski_precond_apply', self._h, dev_ptr(B), dev_ptr(out), B.shape[0],
+                      self.lib.stream_ptr(self.device))
+        return out
+
     def mvm(self, X, out=None):
         if out is None:
             out = torch.empty_like(X)
@@ -504,6 +526,46 @@ def row_dots(lib, B, X):
     lib.call('rl_row_dots', dev_ptr(B), dev_ptr(X), int(k), int(n), dev_ptr(out[0]),
              dev_ptr(out[1]), dev_ptr(ws), lib.stream_ptr(B.device))
     return out[0], out[1]
+
+
+LOO_PARTIALS = 256      # include/runlmc_hip.h: RL_LOO_PARTIALS
+
+
+def diag_accumulate(lib, Z, X, C, sum, sumsq):
+    """sum[i] += t, sumsq[i] += t^2 for t = Z[v, i] (X[v, i] - C[v, i]), v ascending, in place
+    (rl_diag_accumulate).  Z, X, C: (k, n) device tensors, C may be None; sum, sumsq: (n,)."""
+    if Z.dim() != 2 or X.shape != Z.shape or (C is not None and C.shape != Z.shape):
+        raise ValueError('diag_accumulate: Z, X and C must be (k, n) tensors of one shape')
+    k, n = Z.shape
+    if sum.shape != (n,) or sumsq.shape != (n,):
+        raise ValueError('diag_accumulate: sum and sumsq must have %d entries' % n)
+    lib.call('rl_diag_accumulate', dev_ptr(Z), dev_ptr(X),
+             dev_ptr(C) if C is not None else ctypes.c_void_p(0), int(k), int(n),
+             dev_ptr(sum), dev_ptr(sumsq), lib.stream_ptr(Z.device))
+    return sum, sumsq
+
+
+def loo_reduce(lib, y, alpha, dinv, logscale=None):
+    """(mean, var, logp, bad): leave-one-out means y - alpha / d and variances 1 / d as device
+    tensors (n,), the sum of the log densities of y under them (minus logscale per row) and
+    the count of rows whose d is not a positive finite number -- those hold NaN and are left
+    out of the sum (rl_loo_reduce; the block sums are added here in block order)."""
+    n = y.shape[0]
+    for t in (alpha, dinv) + ((logscale,) if logscale is not None else ()):
+        if t.shape != (n,) or y.dim() != 1:
+            raise ValueError('loo_reduce: y, alpha, dinv and logscale must be vectors of one length')
+    mean, var = torch.empty_like(y), torch.empty_like(y)
+    part = torch.zeros((2, LOO_PARTIALS), dtype=torch.float64, device=y.device)
+    nblk = ctypes.c_int()
+    lib.call('rl_loo_reduce', dev_ptr(y), dev_ptr(alpha), dev_ptr(dinv),
+             dev_ptr(logscale) if logscale is not None else ctypes.c_void_p(0), int(n),
+             dev_ptr(mean), dev_ptr(var), dev_ptr(part), ctypes.byref(nblk),
+             lib.stream_ptr(y.device))
+    host = part.cpu().numpy()
+    logp = 0.0
+    for b in range(nblk.value):
+        logp += float(host[0, b])
+    return mean, var, logp, int(round(host[1, :nblk.value].sum()))
 
 
 # ---- exact (dense) likelihood: include/runlmc_hip.h rl_exact_* ----------------------------------

@@ -5,11 +5,12 @@ builds every b_t on the host and solves them one by one in a process pool).
 A tile of `batch` rows is written straight into device memory by a row source, solved with
 ``Iterative.solve_device`` (so that the operator's ``preconditioner`` is honoured exactly as in
 training) and reduced on the device (rl_row_dots); only O(batch) scalars per tile reach the
-host.  Two row sources:
+host.  Row sources:
 
 * :class:`CrossRows`   b_t = K_exact(x_t, X)      -- 'on-the-fly' variances (rl_exact_cross_dev);
 * :class:`GridColumnRows`   b_i = W K_UU e_i      -- 'precompute': nu_i = (K_UU W^T K~^-1 W K_UU)_ii
-  = b_i^T K~^-1 b_i, since K_UU and K~^-1 are symmetric.
+  = b_i^T K~^-1 b_i, since K_UU and K~^-1 are symmetric;
+* :class:`UnitRows`   b_t = e_i                    -- (K~^-1)_ii, leave-one-out (approx/loo.py).
 """
 import collections
 import logging
@@ -70,6 +71,37 @@ class GridColumnRows:
         E = torch.zeros((nrows, self.grid.width), dtype=torch.float64, device=dev)
         E[torch.arange(nrows, device=dev), idx] = 1.0
         return self.ski.apply_w(self.grid.mvm(E), term=0)
+
+
+class UnitRows:
+    """b_t = e_i(t): one-hot training rows written on the device, so that quad_forms gives
+    (K~^-1)_ii for the indices asked for (default: every row in order) -- leave-one-out
+    cross-validation on operators without a factorisation (approx/loo.py)."""
+
+    def __init__(self, n, indices=None, device=None):
+        self.n = int(n)
+        self.device = device
+        if indices is None:
+            self.indices = None
+            self.total_rows = self.n
+        else:
+            raw = np.asarray(indices)
+            if raw.size and (raw.dtype == bool or not np.issubdtype(raw.dtype, np.integer)):
+                raise ValueError('row indices must be integers, got dtype %s' % raw.dtype)
+            idx = raw.astype(np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= self.n):
+                raise ValueError('row indices must lie in [0, %d)' % self.n)
+            self.indices = torch.from_numpy(idx).to(device)
+            self.total_rows = idx.size
+
+    def fill(self, row0, nrows):
+        if self.indices is None:
+            idx = torch.arange(row0, row0 + nrows, device=self.device)
+        else:
+            idx = self.indices[row0:row0 + nrows]
+        E = torch.zeros((nrows, self.n), dtype=torch.float64, device=self.device)
+        E[torch.arange(nrows, device=self.device), idx] = 1.0
+        return E
 
 
 def _solver_name(K):

@@ -4,6 +4,7 @@
 #include "rl_host.h"
 #include "rl_solver.h"
 #include "rl_direct.h"
+#include "rl_loo.h"
 
 void free_work(SolverWork& w) {
     for (double*& p : w.vec) { if (p) (void)hipFree(p); p = nullptr; }
@@ -2089,6 +2090,98 @@ extern "C" int rl_ski_precond_sample(rl_ski* s, const double* Win, double* Rout,
     RL_TRY(dz_apply(s, s->dz_smp, Ri, nvec, st, (const double*)s->dz_Zh, (const double*)s->noise_diag));
     if (s->permuted) permute_rows(s, Ri, Rout, nvec, 1, st);
     RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Leave-one-out cross-validation (rl_loo.h)
+// ---------------------------------------------------------------------------
+// out[i] = (A^-1)_ii, A the matrix the factorisation inverts: K~ (*exact = 1) or its projection P
+// on the polynomial subspace (*exact = 0) -- one pass over the table of F, no solve
+extern "C" int rl_ski_inverse_diag(rl_ski* s, double* out, int* exact, void* stream) {
+    if (!s || !out || !exact) return fail(RL_EINVAL, "rl_ski_inverse_diag: NULL argument");
+    rl_gridop* g = s->g;
+    bool ok = false;
+    const char* why = "";
+    RL_TRY(dz_ensure(s, &ok, &why));
+    if (!ok) return fail(RL_ELIMIT, std::string("rl_ski_inverse_diag: no factorisation for this operator: ") + why);
+    if (s->dz_hz)
+        return fail(RL_ELIMIT, "rl_ski_inverse_diag: the factorisation is on the 96-function basis, whose map is "
+                               "kept in blocks of 48 functions: no diagonal from it");
+    if (s->rp_F == nullptr || s->rp_R != g->lr_r || s->dz_R != g->lr_r || s->dz_Zt == nullptr || s->dz_inv == nullptr)
+        return fail(RL_ELIMIT, "rl_ski_inverse_diag: the table of F does not match the factorisation");
+    RL_HIP(hipSetDevice(g->device));
+    hipStream_t st = (hipStream_t)stream;
+    (void)st;                              // (the emulator's launch takes no stream)
+    const int* perm = s->permuted ? (const int*)s->perm : (const int*)nullptr;
+#define RL_DZ_DIAG(R_)                                                                             \
+    RL_LAUNCH((k_dz_diag<R_>), dim3((s->n + 255) / 256), dim3(256), 0, st, (const double*)s->rp_F, s->n, \
+              g->D, (const int*)s->rp_out_end, (const double*)s->dz_Zt, (const double*)s->dz_inv, perm, out)
+    RL_DZ_RANKS(RL_DZ_DIAG);
+#undef RL_DZ_DIAG
+    RL_HIP(hipGetLastError());
+    *exact = s->dz_exact ? 1 : 0;
+    return RL_OK;
+}
+
+// X = P^-1 B: ONE application of the factorisation (dz_apply, what rl_solve_pcg applies every
+// iteration), caller's row order
+extern "C" int rl_ski_precond_apply(rl_ski* s, const double* B, double* X, int nvec, void* stream) {
+    if (!s || !B || !X) return fail(RL_EINVAL, "rl_ski_precond_apply: NULL argument");
+    if (nvec < 0) return fail(RL_EINVAL, "rl_ski_precond_apply: nvec < 0");
+    if (B == X) return fail(RL_EINVAL, "rl_ski_precond_apply: B and X may not alias");
+    rl_gridop* g = s->g;
+    bool ok = false;
+    const char* why = "";
+    RL_TRY(dz_ensure(s, &ok, &why));
+    if (!ok) return fail(RL_ELIMIT, std::string("rl_ski_precond_apply: no factorisation for this operator: ") + why);
+    if (nvec == 0) return RL_OK;
+    RL_HIP(hipSetDevice(g->device));
+    hipStream_t st = (hipStream_t)stream;
+    RL_TRY(rp_prepare(s, std::max(nvec, g->lr_r)));
+    RL_TRY(ski_reserve_perm(s, nvec));
+    if (s->dz_hz) RL_TRY(hz_reserve(s, nvec));
+    RL_TRY(lr_reserve(g, nvec));
+    const double* Bi = B;
+    double* Xi = X;
+    if (s->permuted) {
+        permute_rows(s, B, s->P1, nvec, 0, st);
+        Bi = s->P1;
+        Xi = s->P2;
+    }
+    RL_TRY(dz_apply(s, Bi, Xi, nvec, st));
+    if (s->permuted) permute_rows(s, Xi, X, nvec, 1, st);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+extern "C" int rl_diag_accumulate(const double* Z, const double* X, const double* C, int nvec, long long n,
+                                  double* sum, double* sumsq, void* stream) {
+    if (!Z || !X || !sum || !sumsq) return fail(RL_EINVAL, "rl_diag_accumulate: NULL argument");
+    if (nvec < 0 || n < 1) return fail(RL_EINVAL, "rl_diag_accumulate: bad sizes");
+    if (sum == sumsq) return fail(RL_EINVAL, "rl_diag_accumulate: sum and sumsq may not alias");
+    if (n > 256LL * 2147483647LL) return fail(RL_ELIMIT, "rl_diag_accumulate: n beyond one launch");
+    if (nvec == 0) return RL_OK;
+    RL_LAUNCH(k_loo_accumulate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, Z, X, C,
+              nvec, n, sum, sumsq);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+extern "C" int rl_loo_reduce(const double* y, const double* alpha, const double* dinv, const double* logscale,
+                             long long n, double* mean, double* var, double* logp_partials, int* nblk,
+                             void* stream) {
+    if (!y || !alpha || !dinv || !mean || !var || !logp_partials || !nblk)
+        return fail(RL_EINVAL, "rl_loo_reduce: NULL argument");
+    if (n < 1) return fail(RL_EINVAL, "rl_loo_reduce: n < 1");
+    if (mean == var) return fail(RL_EINVAL, "rl_loo_reduce: mean and var may not alias");
+    if (dinv == mean || dinv == var || alpha == mean || alpha == var || y == mean || y == var)
+        return fail(RL_EINVAL, "rl_loo_reduce: an output may not alias an input");
+    const int nb = (int)std::max<long long>(1, std::min<long long>(RL_LOO_PARTIALS, (n + 1023) / 1024));
+    RL_LAUNCH(k_loo_reduce, dim3(nb), dim3(256), 2 * 256 * sizeof(double), (hipStream_t)stream, y, alpha, dinv,
+              logscale, n, mean, var, logp_partials);
+    RL_HIP(hipGetLastError());
+    *nblk = nb;
     return RL_OK;
 }
 

@@ -99,6 +99,9 @@ class InterpolatedLLGP:
         self.variance_tolerance = 1e-4
         # what the last tiled variance computation returned per row (approx.quadforms.QuadForms)
         self.variance_stats = None
+        # what the last leave-one-out call used: method, sem, solver statistics, count of rows
+        # with a non-positive diagonal entry (loo_predict)
+        self.loo_stats = None
         self._functional_kernel = functional_kernel
         self._functional_kernel.set_input_dim(self.input_dim)
         if any(len(ad) > 2 for ad in functional_kernel.active_dims):
@@ -534,6 +537,76 @@ class InterpolatedLLGP:
         if len(Xs) != self.output_dim:
             raise ValueError('need one (possibly empty) input array per output')
         return self.posterior_draws(size, seed=seed, **kw)(Xs, noise=noise)
+
+    # -- leave-one-out cross-validation (no reference twin; approx/loo.py) -----------------------
+    def _loo(self, indices, method, kw):
+        """(means, variances, log density sum) of the held-out observations, in the units of the
+        original Ys: tensors over all rows, or over `indices`.  Fills loo_stats."""
+        from ..approx.loo import inverse_diagonal
+        from .._native import loo_reduce
+        self._ensure()
+        K = self._K
+        dev, lib = K.device, K.device_operator().lib
+        res = inverse_diagonal(K, method=method, indices=indices, **kw)
+        lens = [len(Y) for Y in self.Ys]
+
+        def rows(v):
+            return torch.from_numpy(np.ascontiguousarray(v, dtype=np.float64)).to(dev)
+        alpha = getattr(getattr(self.kernel, 'deriv', None), 'alpha_dev', None)
+        if alpha is None:
+            alpha = rows(self.kernel.alpha())
+        y = rows(self.y)
+        sd = np.repeat([s for _, s in self.normalizer], lens) if self.normalizer else None
+        mu = np.repeat([m for m, _ in self.normalizer], lens) if self.normalizer else None
+        sel = None
+        if indices is not None:
+            sel = np.asarray(indices, dtype=np.int64).reshape(-1)
+            if sel.size == 0:
+                self.loo_stats = dict(method=res.method, sem=res.sem, stats=res.stats, nonpositive=0)
+                return np.zeros(0), np.zeros(0), 0.0
+            at = torch.from_numpy(sel).to(dev)
+            alpha, y = alpha[at].contiguous(), y[at].contiguous()
+            if sd is not None:
+                sd, mu = sd[sel], mu[sel]
+        logscale = rows(np.log(sd)) if sd is not None else None
+        mean, var, logp, bad = loo_reduce(lib, y, alpha.contiguous(), res.d.contiguous(), logscale)
+        if bad:
+            _LOG.critical('leave-one-out (%s): %d of %d rows have a diagonal entry of K~^-1 that is '
+                          'not a positive finite number; their predictions are NaN and they are '
+                          'left out of the log likelihood', res.method, bad, int(y.shape[0]))
+        self.loo_stats = dict(method=res.method, sem=res.sem, stats=res.stats, nonpositive=bad)
+        mean, var = mean.cpu().numpy(), var.cpu().numpy()
+        if sd is not None:
+            mean, var = mean * sd + mu, var * sd ** 2
+        return mean, var, logp
+
+    def loo_predict(self, indices=None, method='auto', **kw):
+        """(means, variances) of every training OBSERVATION predicted from all the others
+        (leave-one-out, Rasmussen & Williams 5.4.2): mean y_i - alpha_i / d_i and variance
+        1 / d_i with d = diag(K~^-1), de-normalised as ``predict`` de-normalises.  One array per
+        output; with `indices` (rows of the concatenated outputs) two arrays over those rows.
+
+        The held-out quantity is the noisy observation, so the noise is part of the variance:
+        ``variances[d] - noise_d * sd_d ** 2`` is the latent function's (sd_d = 1 without
+        normalisation).
+
+        method and **kw (probes, n_probes, seed, batch, tol, control_variate) go to
+        ``approx.loo.inverse_diagonal``: 'direct' (no solve at all, operators whose factorisation
+        is K~^-1), 'solve' (one solve per row asked for), 'probes' (an estimate; ``loo_stats['sem']``
+        is the standard error of d), 'auto'.  alpha is the solve the model has already made.
+        ``loo_stats`` holds the method that ran, sem, the solver's statistics and the count of
+        rows with a non-positive d (logged at CRITICAL, NaN in the result, never clamped)."""
+        mean, var, _ = self._loo(indices, method, kw)
+        if indices is not None:
+            return mean, var
+        cuts = np.cumsum([len(Y) for Y in self.Ys])[:-1]
+        return np.split(mean, cuts), np.split(var, cuts)
+
+    def loo_log_likelihood(self, indices=None, method='auto', **kw):
+        """The leave-one-out pseudo-likelihood: sum over the rows (or over `indices`) of the log
+        density of y_i under its leave-one-out prediction, in the units of the original Ys (a
+        normalising model subtracts log sd_d per row).  Arguments as loo_predict."""
+        return float(self._loo(indices, method, kw)[2])
 
     def predict_quantiles(self, Xs, quantiles=(2.5, 97.5)):
         """Gaussian predictive quantiles (multigp.py:152-174)."""
