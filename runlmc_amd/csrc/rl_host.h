@@ -414,7 +414,8 @@ struct rl_ski {
     int dz_fail_streak = 0, dz_fail_skip = 0;   // back-off of the attempts after failures in a row
     double *dz_p = nullptr, *dz_q = nullptr;       // dev [cap][n]: PCG's direction and operator product
     size_t dz_pq_cap = 0;
-    double* dz_scal = nullptr;          // dev [cap][2]: PCG's (rho, rho_prev)
+    double* dz_scal = nullptr;          // dev [dz_scal_cap][2]: PCG's (rho, rho_prev)
+    size_t dz_scal_cap = 0;             // (its own: rl_solve_direct grows dz_part / dz_go without it)
     unsigned long long dz_param_ver = 0, dz_noise_ver = 0;
     int dz_R = 0;
     // the 96-function preconditioner of an operator without a polynomial row (rl_solve.hip: hz_*)

@@ -1882,18 +1882,25 @@ static int pcg_core(rl_ski* s, const double* B, double* X, int nrhs, double tol,
         RL_HIP(hipMalloc((void**)&s->dz_q, ve * sizeof(double)));
         s->dz_pq_cap = ve;
     }
-    if (s->dz_rhs_cap < (size_t)nrhs || s->dz_scal == nullptr) {
+    if (s->dz_rhs_cap < (size_t)nrhs) {
         if (s->dz_part) RL_HIP(hipFree(s->dz_part));
         if (s->dz_go) RL_HIP(hipFree(s->dz_go));
-        if (s->dz_scal) RL_HIP(hipFree(s->dz_scal));
         s->dz_part = nullptr;
         s->dz_go = nullptr;
-        s->dz_scal = nullptr;
         s->dz_rhs_cap = 0;
         RL_HIP(hipMalloc((void**)&s->dz_part, (size_t)nrhs * (2 * RL_DZ_NBLK + 1) * sizeof(double)));
         RL_HIP(hipMalloc((void**)&s->dz_go, (size_t)nrhs * sizeof(int)));
-        RL_HIP(hipMalloc((void**)&s->dz_scal, (size_t)nrhs * 2 * sizeof(double)));
         s->dz_rhs_cap = (size_t)nrhs;
+    }
+    // (dz_scal under a capacity of its own: dz_part / dz_go are shared with rl_solve_direct, which
+    // grows them -- and dz_rhs_cap -- without it.  Sized by dz_rhs_cap, a handle that ran PCG on 3
+    // systems, the direct solver on 39 and PCG on 21 wrote 21 pairs into room for 3)
+    if (s->dz_scal_cap < (size_t)nrhs) {
+        if (s->dz_scal) RL_HIP(hipFree(s->dz_scal));
+        s->dz_scal = nullptr;
+        s->dz_scal_cap = 0;
+        RL_HIP(hipMalloc((void**)&s->dz_scal, (size_t)nrhs * 2 * sizeof(double)));
+        s->dz_scal_cap = (size_t)nrhs;
     }
     const double* Bi = B;
     double* Xi = X;

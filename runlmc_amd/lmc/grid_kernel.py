@@ -126,6 +126,8 @@ class GridKernel(Matrix):
                           device_index=device_index, sizes=grid_dists.shape)
         self._set(fk, kidx, tops)
         self._skiop = SkiOp(self._op, interpolant, interpolantT)
+        # parameter sets this object has taken since it was built (LMCOperator.state_version)
+        self.version = 0
         self.grid_K = _GridKUU(self._op)
         self.ski = _DeviceSKI(self._skiop, interpolant, interpolantT, self.grid_K)
 
@@ -137,6 +139,7 @@ class GridKernel(Matrix):
         tops = as_f64(fk.eval_kernels_fixed_dim(np.asarray(grid_dists),
                                                 self.active_dim)).reshape(len(kidx), -1)
         self._set(fk, kidx, tops)
+        self.version += 1
 
     def _set(self, fk, kidx, tops):
         vecs = [fk.coreg_vecs[q] for q in kidx]
@@ -176,14 +179,39 @@ class FactoredInverse(Matrix):
 
     MAX_REFINE = 4
 
-    def __init__(self, skiop, exact=True):
+    def __init__(self, skiop, exact=True, version=None):
         super().__init__(skiop.n, skiop.n)
         self._skiop = skiop
         # exact: every top row is in the polynomial form and the factorisation IS K~^-1.  Not
         # exact (a Matern row next to smooth ones, Matern rows alone): it inverts the
         # operator's projection on the polynomial subspace -- the M of preconditioned conjugate
         # gradients (rl_solve_pcg), no log det
-        self.exact = bool(exact)
+        self._exact = bool(exact)
+        # version: () -> LMCOperator.state_version() of the operator this was taken from.  The
+        # handle refactors itself after every parameter or noise update, so an object kept
+        # across one always works on the CURRENT operator; which of the two kinds its
+        # factorisation is may have changed with it, and is read again from the handle then
+        self._version = version
+        self._stamp = version() if version is not None else None
+
+    @property
+    def exact(self):
+        """Whether the handle's factorisation is K~^-1 (else a preconditioner) for the operator's
+        CURRENT parameters: the flag of construction until a parameter or noise update, read from
+        the handle again after one.  RuntimeError when the current parameters have no
+        factorisation at all."""
+        if self._version is not None:
+            now = self._version()
+            if now != self._stamp:
+                ok = self._skiop.factor()[0]
+                if not ok:
+                    raise RuntimeError(
+                        'this FactoredInverse was taken before a parameter or noise update, and the '
+                        'operator has no factorisation for its current parameters (%s): ask '
+                        'K.preconditioner again' % self._skiop.factor_reason)
+                self._exact = self._skiop.factor_mode == 1
+                self._stamp = now
+        return self._exact
 
     def solve(self, B, tol=1e-4, max_refine=None, maxiter=0):
         """B: (k, n) tensor on the device.  (X, applications of the factorisation, residuals,
@@ -268,6 +296,14 @@ class LMCOperator(SumMatrix):
             self.term_of[gk.active_dim] = self._skiop.add_term(gk._op, W, WT)
         self._skiop.set_noise(noise, lens)
         self.lens = list(lens)
+        self._noise_version = 0
+
+    def state_version(self):
+        """A value that changes with every GridKernel.update() of a term and every
+        update_noise(): what an object derived from the operator's parameters keeps to find out
+        later whether it still describes them (StochasticDeriv's deferred log det,
+        FactoredInverse.exact)."""
+        return tuple(gk.version for gk in self._gks), self._noise_version
 
     def device_operator(self):
         return self._skiop
@@ -279,7 +315,8 @@ class LMCOperator(SumMatrix):
         polynomial form (the factorisation is rebuilt on the device handle whenever
         parameters or noise changed), else None -- the Krylov path as before."""
         ok = self._skiop.factor()[0]
-        return FactoredInverse(self._skiop, exact=self._skiop.factor_mode == 1) if ok else None
+        return (FactoredInverse(self._skiop, exact=self._skiop.factor_mode == 1,
+                                version=self.state_version) if ok else None)
 
     @property
     def device(self):
@@ -303,6 +340,7 @@ class LMCOperator(SumMatrix):
     def update_noise(self, noise, lens):
         self._skiop.set_noise(noise, lens)
         self.Ks[-1].v = np.repeat(noise, lens)
+        self._noise_version += 1
 
 
 def gen_grid_kernel(fk, grid_dists, interpolants, lens_per_output,

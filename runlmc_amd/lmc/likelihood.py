@@ -165,6 +165,13 @@ class ApproxLMCLikelihood(LMCLikelihood):
         fk = self.functional_kernel
         D, Q = fk.D, fk.Q
         dv = self.deriv
+        # (the Gram terms below read the operator's handle -- its interpolants, and in the
+        # coefficient space the maps C_q of its CURRENT parameters)
+        unchanged = getattr(dv, 'operator_unchanged', None)
+        if unchanged is not None and not unchanged():
+            raise RuntimeError('the gradients of this likelihood were never asked for, and its operator '
+                               'has taken a parameter or noise update since the solves: they can no '
+                               'longer be evaluated for the parameters of these solves')
         skiop = self.K.device_operator()
         lib, dev = skiop.lib, skiop.device
         term_of = getattr(self.K, 'term_of', None) or {ad: 0 for ad in fk.active_dims}

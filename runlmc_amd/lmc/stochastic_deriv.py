@@ -92,6 +92,11 @@ class StochasticDerivService:
             raise ValueError('probes must have shape {}'.format((self._n_it, n)))
         mine = shard_rows(self._n_it, self._group)
         dev = K.device
+        # the parameter state of the operator these solves are made with: whatever is evaluated
+        # later from the operator itself (the deferred log det below, the likelihood's Gram
+        # terms) checks that it is still that state
+        version = getattr(K, 'state_version', None)
+        stamp = version() if version is not None else None
         # Every rank solves for alpha next to its own probes (no rank waits
         # for another during the solve); y rides in a transform pair of its
         # own -- last in an odd batch, or next to a zero vector -- so that its
@@ -215,7 +220,18 @@ class StochasticDerivService:
                 # ran and the factorisation's log det is not the operator's -- asked for, the log
                 # det comes from a few extra preconditioned solves, FactoredInverse.logdet_estimate)
                 tol, grp = self._tol, self._group
-                logdet_fn = lambda: M.logdet_estimate(tol=tol, group=grp)    # noqa: E731
+
+                def logdet_fn():
+                    # (M works on the LIVE handle: after gk.update() / update_noise() the
+                    # estimate would be another operator's log det next to this object's alpha)
+                    if version is not None and version() != stamp:
+                        raise RuntimeError(
+                            'the log det of this StochasticDeriv was deferred and never asked for, '
+                            'and the operator has taken a parameter or noise update since the '
+                            'solves (state %r, now %r): it can no longer be evaluated for the '
+                            'parameters of these solves -- call log_det_K() before the update, or '
+                            'build a new likelihood' % (stamp, version()))
+                    return M.logdet_estimate(tol=tol, group=grp)
         else:
             lanczos = lanczos[order]
         if self.metrics is not None:
@@ -230,7 +246,8 @@ class StochasticDerivService:
         broadcast_(alpha, src=0, group=self._group)        # (no-op in a world of one)
         return StochasticDeriv(alpha, B[1:], X[1:], self._n_it, group=self._group,
                                iterations=iters, residuals=resid, istop=istop,
-                               lanczos=lanczos, logdet_exact=logdet_exact, logdet_fn=logdet_fn)
+                               lanczos=lanczos, logdet_exact=logdet_exact, logdet_fn=logdet_fn,
+                               operator_state=(version, stamp))
 
     def _concurrent_solve(self, ls):
         """Reference entry point (stochastic_deriv.py:51-52): a list of
@@ -251,7 +268,8 @@ class StochasticDeriv(Derivative):
     ``n_it`` is the GLOBAL probe count (the 1/N of the estimator)."""
 
     def __init__(self, alpha, rs, inv_rs, n_it, group=None, iterations=None,
-                 residuals=None, istop=None, lanczos=None, logdet_exact=None, logdet_fn=None):
+                 residuals=None, istop=None, lanczos=None, logdet_exact=None, logdet_fn=None,
+                 operator_state=None):
         to_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(
             np.ascontiguousarray(a, dtype=np.float64))
         self.alpha_dev = to_t(alpha)
@@ -265,6 +283,16 @@ class StochasticDeriv(Derivative):
         self._logdet_fn = logdet_fn          # () -> (estimate, sem, iterations), run on first use
         self.logdet_precond = None           # its result, once asked for
         self._alpha_host = None
+        # (callable, value at the solves) of LMCOperator.state_version, or None
+        self._operator_state = operator_state
+
+    def operator_unchanged(self):
+        """False once the operator these solves were made with has taken a parameter or noise
+        update (True for operators that keep no version)."""
+        if self._operator_state is None or self._operator_state[0] is None:
+            return True
+        version, stamp = self._operator_state
+        return version() == stamp
 
     @property
     def alpha(self):
