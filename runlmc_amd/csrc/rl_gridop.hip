@@ -98,6 +98,7 @@ RlKnobs read_knobs() {
     k.no_rp = flag("RUNLMC_NO_RP");
     k.rp_stagger = (int)num("RUNLMC_RP_STAGGER", 7);
     k.no_lr_small = flag("RUNLMC_NO_LR_SMALL");
+    k.lr_expand_plain = (int)num("RUNLMC_LR_EXPAND_PLAIN", 0);
     k.no_precond_approx = flag("RUNLMC_NO_PRECOND_APPROX");
     k.no_precond_hi = flag("RUNLMC_NO_PRECOND_HI");
     k.precond_hi_passes = flag("RUNLMC_PRECOND_HI_PASSES");
@@ -1383,25 +1384,12 @@ static void lr_mix(rl_gridop* g, const double* part, int chunks, int nvec, int Q
 template <int R>
 static void lr_expand(rl_gridop* g, const double* zhat, int nrows, double* Y, int accumulate,
                       hipStream_t st) {
-    // rows per expansion workgroup: the basis values of a slot are generated once
-    // per workgroup (48 instructions against 14 per row and slot).  16 rows when
-    // that makes at least two resident rounds of workgroups (measured at C5, 1290
-    // rows, row blocks numbered fastest: 4 / 8 / 16 / 32 rows: 200-211 us, flat),
-    // otherwise as many row blocks as make one round.  Resident workgroups per
-    // CU: 8 (58 VGPRs).
+    // 16 rows per workgroup (the basis values of a slot are generated once per workgroup: 48
+    // instructions against 14 per row and slot), 8 resident workgroups per CU (58 VGPRs): the
+    // rule and its measurement are at lr_expand_rpb, rl_lowrank.h
     const int per_cu = 8;
-    const int nbx = ((g->m + 1) / 2 + 255) / 256;        // slots: a point and its mirror
-    int rpb = 16;
-    if ((size_t)nbx * ((nrows + 15) / 16) < (size_t)2 * per_cu * RL_LR_CUS) {
-        const int nby = std::max(1, std::min(nrows, per_cu * RL_LR_CUS / nbx));
-        rpb = (nrows + nby - 1) / nby;
-    }
-    if (accumulate)
-        RL_LAUNCH((k_lr_expand<R, true>), dim3(nbx, (nrows + rpb - 1) / rpb), dim3(256), 0,
-                  st, zhat, nrows, g->m, (const double*)g->lr_beta, rpb, Y);
-    else
-        RL_LAUNCH((k_lr_expand<R, false>), dim3(nbx, (nrows + rpb - 1) / rpb), dim3(256), 0,
-                  st, zhat, nrows, g->m, (const double*)g->lr_beta, rpb, Y);
+    lr_expand_launch<R>(zhat, nrows, g->m, (const double*)g->lr_beta, Y, accumulate != 0, 16,
+                        per_cu * RL_LR_CUS, g->kn.lr_expand_plain, st);
 }
 template <int R>
 static void lr_launch(rl_gridop* g, const double* X, double* Y, int nvec, int Q, const double* Cq,

@@ -91,6 +91,10 @@ struct RlKnobs {
                                  // C5 matern round 3.71 ms against 4.18, mix 3.98 against 4.41
     bool no_rp_fuse = false;     // RUNLMC_NO_RP_FUSE: MINRES's B as its own kernel in row-polynomial rounds
     bool no_lr_small = false;    // RUNLMC_NO_LR_SMALL: small batches never take k_lr_small_*
+    int lr_expand_plain = 0;     // RUNLMC_LR_EXPAND_PLAIN: 1 k_lr_expand whatever the row length (never
+                                 // k_lr_expand_lines: A/B runs, the bit-equality tests), 2 the same with
+                                 // its row blocks padded to a multiple of 8 (what k_lr_expand_lines is held against)
+                                 // 3 k_lr_expand_lines also where it is not the default (rank >= 36, accumulating)
     bool no_precond_approx = false;   // RUNLMC_NO_PRECOND_APPROX: no preconditioner for operators outside the polynomial form
     long long precond_hi_min = 100000;   // RUNLMC_PRECOND_HI_MIN: rows from which an operator without a polynomial row
                                       // gets the 96-function preconditioner

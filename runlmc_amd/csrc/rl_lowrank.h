@@ -335,6 +335,9 @@ k_lr_mix(const double* __restrict__ part, int nchunks, int nvec, int D, int r, i
 // out --, non-temporal stores 271 vs 243.  Round 3: the expansion of the larger
 // ranks on the fp64 matrix cores -- Zhat fragments in registers, the chunk's basis in
 // LDS, 16 rows x 16 slots per tile, 128-byte stores: 555 vs 330-370 us at rank 48.)
+// This kernel runs when rows start on 128-byte lines (16 divides m, Y line-aligned) and under
+// RUNLMC_LR_EXPAND_PLAIN; every other row length takes k_lr_expand_lines below (lr_expand_launch).
+// (A row block past the last row -- a padded gridDim.y -- has an empty row loop.)
 // ---------------------------------------------------------------------------
 // (ACC is a template parameter, not a run-time flag: with the read of Y behind a run-time
 // condition the compiler waited for EVERY outstanding access before each of the two stores
@@ -399,6 +402,151 @@ k_lr_expand(const double* __restrict__ Zhat, int nrows, int m, const double* __r
         if (live) *y0 = (ev + od) + o0;
         if (pair) *y1 = (ev - od) + o1;
     }
+}
+
+// ---------------------------------------------------------------------------
+// k_lr_expand_lines<R, ACC>: the same expansion -- the same recurrence, the same even / odd sums
+// of a slot and its mirror, bit for bit -- with another assignment of SLOTS to threads, for rows
+// that do not start on a 128-byte line.  At m = 100 004 (C5) a row starts 32 bytes past a line
+// three times out of four: every 512-byte wave store of k_lr_expand touches five lines, two of
+// them partially, and the end lines of a block's segment are shared with the neighbouring
+// column block.
+//   p0 = (Y / 8) mod 16 (taken from the pointer: a view is 8-byte aligned only),
+//   phase(row) = (p0 + row m) mod 16, periodic in the row with P = 16 / gcd(m mod 16, 16).
+// A workgroup takes rows_per_block rows of ONE class c, c + P, c + 2 P, ...: the phase is the
+// same for every row of the block, the basis values are generated once and the coefficients
+// come through scalar loads (stride P R).  Thread tid of column block bx owns slot
+// n = 256 bx + tid - phase: its ascending element sits at tid mod 16 within a line -- a wave
+// stores four whole lines.  Lanes with n < 0 or n >= slots are dead; column blocks:
+// ceil((slots + 15) / 256).  The mirror element leaves from the same thread, as in k_lr_expand
+// (its wave store touches five lines).
+//   grid (nbx, nby_pad)   block 256
+// Row blocks are numbered fastest (as in k_lr_expand) and by = kb P + c < nby; the host pads
+// gridDim.y to a multiple of 8 so that the column neighbours (bx, by), (bx + 1, by) -- which
+// share the end lines of their mirror segments -- run on one XCD; the surplus workgroups leave
+// at once.
+// (Measured and kept out of the library, profiles/expand_lines: the mirror half through 4 KB of
+// LDS so that it leaves in whole lines too -- one barrier per row; 187-190 us at C5 against
+// 185-186 without it.  tools/lr_pattern_probe.hip holds that variant.)
+// ---------------------------------------------------------------------------
+template <int R, bool ACC>
+__global__ void __launch_bounds__(256)
+k_lr_expand_lines(const double* __restrict__ Zhat, int nrows, int m, const double* __restrict__ beta,
+                  int rows_per_block, int period, int nby, double* __restrict__ Y) {
+    const int slots = lr_slots(m);
+    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
+    const int bx = lin / gridDim.y, by = lin - bx * gridDim.y;
+    if (by >= nby) return;                                  // (padding of the row blocks)
+    const int cls = by % period, kb = by / period;
+    const int rfirst = cls + kb * rows_per_block * period;
+    int nr = rfirst < nrows ? (nrows - rfirst + period - 1) / period : 0;   // (a short class: 0)
+    nr = nr < rows_per_block ? nr : rows_per_block;
+    const int p0 = (int)((reinterpret_cast<unsigned long long>(Y) >> 3) & 15ull);
+    const int phase = (p0 + cls * (m & 15)) & 15;
+    const int n = bx * 256 + (int)threadIdx.x - phase;
+    const int nc = n < 0 ? 0 : (n < slots ? n : slots - 1);
+    const int mir = m - 1 - nc;
+    const bool live = n >= 0 && n < slots, pair = live && mir != nc;
+    const double s = lr_point(nc, m);
+    double p[R];
+    {
+        double qm = 0.0, q = 1.0;
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            p[j] = q;
+            const double qn = fma(s, q, -beta[j] * qm);
+            qm = q;
+            q = qn;
+        }
+    }
+    for (int k = 0; k < nr; ++k) {
+        const int row = rfirst + k * period;
+        const double* z = Zhat + (size_t)row * R;
+        double zz[R];               // (ONE batch of scalar loads: k_lr_expand)
+#pragma unroll
+        for (int j = 0; j < R; ++j) zz[j] = z[j];
+#if !defined(RL_EMU)
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+        double ev = 0.0, od = 0.0;
+#pragma unroll
+        for (int j = 0; j + 1 < R; j += 2) {
+            ev = fma(zz[j], p[j], ev);
+            od = fma(zz[j + 1], p[j + 1], od);
+        }
+        double* y0 = Y + (size_t)row * m + nc;
+        double* y1 = Y + (size_t)row * m + mir;
+        double o0 = 0.0, o1 = 0.0;
+        if constexpr (ACC) {
+            o0 = *y0;
+            o1 = *y1;
+        }
+        if (live) *y0 = (ev + od) + o0;
+        if (pair) *y1 = (ev - od) + o1;
+    }
+}
+
+// Host side: ONE launcher of the expansion for every call site.  `rpb_max` rows per workgroup
+// (0: no such preference) when that makes at least two rounds of `round_wgs` resident
+// workgroups, otherwise as many row blocks as make one round -- the rule of each call site,
+// applied to all rows (k_lr_expand) or to the rows of a class (k_lr_expand_lines).  (Measured at
+// C5 for k_lr_expand, 1290 rows, row blocks numbered fastest: 4 / 8 / 16 / 32 rows per
+// workgroup 200-211 us, flat.)
+struct LrLinesGrid {
+    int nbx, nby, rpb, period;
+};
+static inline int lr_expand_rpb(int nbx, int nr, int ncls, int rpb_max, int round_wgs) {
+    if (rpb_max > 0 &&
+        (size_t)nbx * ncls * ((nr + rpb_max - 1) / rpb_max) >= (size_t)2 * round_wgs)
+        return rpb_max;
+    int nby = round_wgs / (nbx * ncls);
+    nby = nby < nr ? nby : nr;
+    nby = nby > 1 ? nby : 1;
+    return (nr + nby - 1) / nby;
+}
+static inline LrLinesGrid lr_expand_lines_grid(int nrows, int m, int rpb_max, int round_wgs) {
+    LrLinesGrid g;
+    int gcd = 16;
+    while ((m & 15) % gcd != 0) gcd >>= 1;
+    g.period = 16 / gcd;                                 // 1 (16 | m) .. 16 (m odd)
+    g.nbx = ((m + 1) / 2 + 15 + 255) / 256;
+    const int ncr = (nrows + g.period - 1) / g.period;   // rows of the largest class
+    g.rpb = lr_expand_rpb(g.nbx, ncr, g.period, rpb_max, round_wgs);
+    g.nby = g.period * ((ncr + g.rpb - 1) / g.rpb);
+    return g;
+}
+// `plain` (RlKnobs::lr_expand_plain): 0 k_lr_expand_lines unless every phase is 0 -- 16 divides
+// m and Y starts on a line: nothing to gain -- or the instantiation keeps k_lr_expand (below), 1
+// k_lr_expand, 2 k_lr_expand with gridDim.y padded, 3 k_lr_expand_lines for those
+// instantiations too (their tests and A/B runs).  `pad8` is false in the pattern probe only.
+template <int R>
+static void lr_expand_launch(const double* zhat, int nrows, int m, const double* beta, double* Y,
+                             bool accumulate, int rpb_max, int round_wgs, int plain,
+                             hipStream_t st, bool pad8 = true) {
+    const int p0 = (int)((reinterpret_cast<unsigned long long>(Y) >> 3) & 15ull);
+    // (k_lr_expand_lines is the default for ranks below 36, not accumulating: the headline's
+    // instantiations.  The others were faster with it too -- profiles/expand_lines, value 3 --
+    // but at rank 24 a padded k_lr_expand does as well, which is the way to go for all of them.)
+    const bool measured = R < 36 && !accumulate;
+    if ((plain != 0 && plain != 3) || (plain == 0 && !measured) || ((m & 15) == 0 && p0 == 0)) {
+        const int nbx = ((m + 1) / 2 + 255) / 256;
+        const int rpb = lr_expand_rpb(nbx, nrows, 1, rpb_max, round_wgs);
+        const int nby = (nrows + rpb - 1) / rpb;
+        const dim3 grid(nbx, plain == 2 ? (nby + 7) / 8 * 8 : nby);
+        if (accumulate)
+            RL_LAUNCH((k_lr_expand<R, true>), grid, dim3(256), 0, st, zhat, nrows, m, beta, rpb, Y);
+        else
+            RL_LAUNCH((k_lr_expand<R, false>), grid, dim3(256), 0, st, zhat, nrows, m, beta, rpb, Y);
+        return;
+    }
+    const LrLinesGrid g = lr_expand_lines_grid(nrows, m, rpb_max, round_wgs);
+    const dim3 grid(g.nbx, pad8 ? (g.nby + 7) / 8 * 8 : g.nby);
+    if (accumulate)
+        RL_LAUNCH((k_lr_expand_lines<R, true>), grid, dim3(256), 0, st, zhat, nrows, m, beta, g.rpb,
+                  g.period, g.nby, Y);
+    else
+        RL_LAUNCH((k_lr_expand_lines<R, false>), grid, dim3(256), 0, st, zhat, nrows, m, beta, g.rpb,
+                  g.period, g.nby, Y);
 }
 
 // ---------------------------------------------------------------------------

@@ -384,16 +384,9 @@ extern "C" int rl_sampler_spectrum_host(const rl_sampler* h, int q, double* out)
 
 template <int R>
 static void smp_expand(rl_sampler* h, double* U, int nrows, bool accumulate, hipStream_t st) {
-    const int slots = (h->m + 1) / 2, nbx = (slots + 255) / 256;
-    const int nby = std::max(1, std::min(nrows, 4 * RL_LR_CUS / nbx));
-    const int rpb = (nrows + nby - 1) / nby;
-    const dim3 grid(nbx, (nrows + rpb - 1) / rpb);
-    if (accumulate)
-        RL_LAUNCH((k_lr_expand<R, true>), grid, dim3(256), 0, st, (const double*)h->zhat, nrows, h->m,
-                  (const double*)h->g->lr_beta, rpb, U);
-    else
-        RL_LAUNCH((k_lr_expand<R, false>), grid, dim3(256), 0, st, (const double*)h->zhat, nrows, h->m,
-                  (const double*)h->g->lr_beta, rpb, U);
+    // (one round of four workgroups per compute unit, whatever the number of rows)
+    lr_expand_launch<R>((const double*)h->zhat, nrows, h->m, (const double*)h->g->lr_beta, U, accumulate,
+                        0, 4 * RL_LR_CUS, h->g->kn.lr_expand_plain, st);
 }
 
 extern "C" int rl_sampler_draw(rl_sampler* h, const double* Z, double* U, int nsamp, void* stream) {

@@ -4,9 +4,16 @@
 // lengths that are / are not multiples of a 128-byte line (m = 100004: rows start 32 bytes
 // past a line boundary three times out of four):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Irunlmc_amd/csrc -o /tmp/lr_pattern_probe tools/lr_pattern_probe.hip
+// Part 4 (`lr_pattern_probe lines`: that part alone) is the ladder of the expansion's STORE mapping,
+// profiles/expand_lines: rung 0 k_lr_expand as it is, rung 1 the ascending half in whole lines by row
+// class (k_lr_expand_lines, mirror half from its own thread), rung 2 the mirror half through LDS (k_probe_expand_staged), rung 3
+// the row blocks padded to a multiple of 8 (column neighbours on one XCD); and, to tell the rungs apart, rung 4
+// = rung 0 + that padding alone (k_lr_expand has nothing to do in a surplus row block), rung 5 = rung 1 + the
+// padding (no LDS: the library's default).  -DPROBE_RUNGS=<bit mask> compiles a subset (default 0x3F: all six).
 #include "rl_kernels.h"
 #include "rl_lowrank.h"
 #include <cstdio>
+#include <string>
 #include <vector>
 #include <algorithm>
 
@@ -197,7 +204,171 @@ static void ceilings() {
     hipFree(a); hipFree(b);
 }
 
-int main() {
+#ifndef PROBE_RUNGS
+#define PROBE_RUNGS 0x3F
+#endif
+// Rungs 2 and 3: k_lr_expand_lines with the MIRROR half through LDS, so that it leaves in whole lines too.
+// Measured (profiles/expand_lines) and kept out of the library: not distinguishable from rung 5.  The block's
+// mirror values are the 256 contiguous elements from E0 = row m + m - 1 - (256 bx + 255 - phase), at line offset
+// b = (2 phase + m) mod 16.  Thread tid leaves ev - od in stage[buf][255 - tid] (two buffers: ONE barrier per
+// row); thread u then takes entry i = (u + h) mod 256, h = (16 - b) mod 16, and stores element E0 + i: waves 0-2
+// store whole lines, the block's two fragments (h and b elements) sit in wave 3.  The trip count of the row loop
+// is the same for every thread of a block and no dead lane leaves before it (the barrier sits inside).
+template <int R>
+__global__ void __launch_bounds__(256)
+k_probe_expand_staged(const double* __restrict__ Zhat, int nrows, int m, const double* __restrict__ beta,
+                      int rows_per_block, int period, int nby, double* __restrict__ Y) {
+    __shared__ double stage[2 * 256];
+    const int slots = lr_slots(m), tid = threadIdx.x;
+    const int lin = blockIdx.y * gridDim.x + blockIdx.x;
+    const int bx = lin / gridDim.y, by = lin - bx * gridDim.y;
+    if (by >= nby) return;
+    const int cls = by % period, kb = by / period;
+    const int rfirst = cls + kb * rows_per_block * period;
+    if (rfirst >= nrows) return;
+    int nr = (nrows - rfirst + period - 1) / period;
+    nr = nr < rows_per_block ? nr : rows_per_block;
+    const int p0 = (int)((reinterpret_cast<unsigned long long>(Y) >> 3) & 15ull);
+    const int phase = (p0 + cls * (m & 15)) & 15;
+    const int n = bx * 256 + tid - phase;
+    const int nc = n < 0 ? 0 : (n < slots ? n : slots - 1);
+    const bool live = n >= 0 && n < slots;
+    // the mirror element this thread STORES: entry i2 of the block's 256
+    const int h = (16 - ((2 * phase + m) & 15)) & 15;
+    const int i2 = (tid + h) & 255;
+    const int n2 = bx * 256 + 255 - i2 - phase;
+    const int n2c = n2 < 0 ? 0 : (n2 < slots ? n2 : slots - 1);
+    const int mir2 = m - 1 - n2c;
+    const bool pair2 = n2 >= 0 && n2 < slots && mir2 != n2c;
+    const double s = lr_point(nc, m);
+    double p[R];
+    {
+        double qm = 0.0, q = 1.0;
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            p[j] = q;
+            const double qn = fma(s, q, -beta[j] * qm);
+            qm = q;
+            q = qn;
+        }
+    }
+    for (int k = 0; k < nr; ++k) {
+        const int row = rfirst + k * period;
+        const double* z = Zhat + (size_t)row * R;
+        double zz[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) zz[j] = z[j];
+        double* yr = Y + (size_t)row * m;
+        __builtin_amdgcn_sched_barrier(0);
+        double ev = 0.0, od = 0.0;
+#pragma unroll
+        for (int j = 0; j + 1 < R; j += 2) {
+            ev = fma(zz[j], p[j], ev);
+            od = fma(zz[j + 1], p[j + 1], od);
+        }
+        double* sb = stage + (k & 1) * 256;
+        sb[255 - tid] = ev - od;
+        if (live) yr[nc] = ev + od;
+        __syncthreads();
+        const double v = sb[i2];
+        if (pair2) yr[mir2] = v;
+    }
+}
+// the expansion of rung RUNG by the library's launch rule (rl_gridop.hip lr_expand); rung 4 is
+// RUNLMC_LR_EXPAND_PLAIN=2
+template <int R, int RUNG>
+static void expand_rung(const double* zhat, int nrows, int m, const double* beta, double* Y) {
+    if constexpr (RUNG == 2 || RUNG == 3) {
+        const int p0 = (int)((reinterpret_cast<unsigned long long>(Y) >> 3) & 15ull);
+        if ((m & 15) == 0 && p0 == 0) {
+            lr_expand_launch<R>(zhat, nrows, m, beta, Y, false, 16, 8 * RL_LR_CUS, 1, 0);
+            return;
+        }
+        const LrLinesGrid g = lr_expand_lines_grid(nrows, m, 16, 8 * RL_LR_CUS);
+        hipLaunchKernelGGL((k_probe_expand_staged<R>), dim3(g.nbx, RUNG == 3 ? (g.nby + 7) / 8 * 8 : g.nby), dim3(256), 0,
+                           0, zhat, nrows, m, beta, g.rpb, g.period, g.nby, Y);
+    } else {
+        lr_expand_launch<R>(zhat, nrows, m, beta, Y, false, 16, 8 * RL_LR_CUS, RUNG == 0 ? 1 : (RUNG == 4 ? 2 : 0), 0,
+                            RUNG == 5);
+    }
+}
+template <int R, int RUNG>
+static void ladder_rung(int m, int nrows, int steps) {
+    if constexpr (((PROBE_RUNGS >> RUNG) & 1) != 0) {
+        double *X, *part, *beta, *zhat;
+        hipMalloc(&X, (size_t)nrows * m * 8);
+        hipMemset(X, 0, (size_t)nrows * m * 8);
+        const int slots = (m + 1) / 2, chunks = (slots + 64 * steps - 1) / (64 * steps);
+        hipMalloc(&part, (size_t)chunks * nrows * R * 8);
+        hipMalloc(&beta, 64 * 8);
+        hipMemset(beta, 0, 64 * 8);
+        hipMalloc(&zhat, (size_t)nrows * R * 8);
+        hipMemset(zhat, 0, (size_t)nrows * R * 8);
+        hipEvent_t e0, e1;
+        hipEventCreate(&e0);
+        hipEventCreate(&e1);
+        std::vector<float> tp, te, tea;
+        for (int rep = 0; rep < 13; ++rep) {
+            float ms;
+            hipEventRecord(e0);
+            hipLaunchKernelGGL((k_lr_project<R>), dim3(chunks, (nrows + RL_LR_ROWS(R) - 1) / RL_LR_ROWS(R)),
+                               dim3(64 * RL_LR_WAVES), (size_t)RL_LR_WAVES * R * 65 * 8, 0, (const double*)X, nrows, m,
+                               (const double*)beta, steps, part);
+            hipEventRecord(e1);
+            hipEventSynchronize(e1);
+            hipEventElapsedTime(&ms, e0, e1);
+            if (rep >= 2) tp.push_back(ms);
+            hipEventRecord(e0);
+            expand_rung<R, RUNG>(zhat, nrows, m, beta, X);
+            hipEventRecord(e1);
+            hipEventSynchronize(e1);
+            hipEventElapsedTime(&ms, e0, e1);
+            if (rep >= 2) te.push_back(ms);
+        }
+        for (int rep = 0; rep < 13; ++rep) {
+            float ms;
+            hipEventRecord(e0);
+            expand_rung<R, RUNG>(zhat, nrows, m, beta, X);
+            hipEventRecord(e1);
+            hipEventSynchronize(e1);
+            hipEventElapsedTime(&ms, e0, e1);
+            if (rep >= 2) tea.push_back(ms);
+        }
+        std::sort(tp.begin(), tp.end());
+        std::sort(te.begin(), te.end());
+        std::sort(tea.begin(), tea.end());
+        const size_t h = tp.size() / 2;
+        printf("rung %d rank %2d m %6d: project %6.1f us | expand %6.1f us (min %6.1f max %6.1f) | pair %6.1f | expand alone %6.1f us\n",
+               RUNG, R, m, 1e3 * tp[h], 1e3 * te[h], 1e3 * te.front(), 1e3 * te.back(), 1e3 * (tp[h] + te[h]),
+               1e3 * tea[h]);
+        fflush(stdout);
+        hipFree(X); hipFree(part); hipFree(beta); hipFree(zhat);
+        hipEventDestroy(e0);
+        hipEventDestroy(e1);
+    }
+}
+template <int R>
+static void ladder(int m, int nrows) {
+    ladder_rung<R, 0>(m, nrows, 32);
+    ladder_rung<R, 1>(m, nrows, 32);
+    ladder_rung<R, 2>(m, nrows, 32);
+    ladder_rung<R, 3>(m, nrows, 32);
+    ladder_rung<R, 4>(m, nrows, 32);
+    ladder_rung<R, 5>(m, nrows, 32);
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "lines") {
+        // (two passes: what moves between them is this box's spread, not a rung)
+        for (int pass = 0; pass < 2; ++pass) {
+            printf("-- pass %d\n", pass);
+            for (int m : {100004, 100000}) {
+                ladder<2>(m, 1290);
+                ladder<24>(m, 1290);
+            }
+        }
+        return 0;
+    }
     ceilings();
     {
         const int m = 100004, nr = 1290;
