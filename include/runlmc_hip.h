@@ -75,7 +75,11 @@ int rl_gridop_create(int device, int D, int m, int max_tops, rl_gridop** out);
  * of Toeplitz blocks, BTTB(top, (m1, m2)) (bttb.py:91-148 with two sizes; grid
  * index i1*m2 + i2, top rows are k_q of the distances to grid point (0, 0)).
  * The embedding is an N1 x N2 two-dimensional circulant, N_k = pow2 >= 2 m_k.
- * Every other entry point is unchanged (m = m1*m2 points per output).        */
+ * Every other entry point is unchanged (m = m1*m2 points per output).
+ * Limits: N_k <= 4096, i.e. at most 2048 points per axis (RL_ELIMIT beyond, from a
+ * host check before any launch).  A row tile of D outputs that exceeds the LDS
+ * (N2 = 1024: D >= 8; 2048: D >= 4; 4096: D >= 2) runs through the one-output
+ * handle and the mix pass described above, as D > 16 does.                    */
 int rl_gridop_create_2d(int device, int D, int m1, int m2, int max_tops, rl_gridop** out);
 int rl_gridop_destroy(rl_gridop* g);
 /* L = N1*N2 and tile parameters actually chosen (any pointer may be NULL). */

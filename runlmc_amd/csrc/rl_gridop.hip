@@ -440,7 +440,16 @@ static int gridop_create_impl(int device, int D, int m, int m1, int m2, int max_
     if ((long)m > (1L << 27)) return fail(RL_ELIMIT, "rl_gridop_create: m too large");
     RL_HIP(hipSetDevice(device));
     set_lds_attrs();
-    if (D > RL_MAX_D) {
+    // 2-D grids keep N2 (no "shrink N2" below: each axis has its own embedding), so a row
+    // tile of D outputs may not fit the LDS where a tile of one output does (N2 = 1024:
+    // D >= 8, 2048: D >= 4, 4096: D >= 2).  Such a grid takes the route of D > RL_MAX_D.
+    bool rows_too_long = false;
+    if (m1 != 0 && D > 1) {      // (m1 * m2 <= 2^27: 2 * m2 fits an int)
+        int n2 = 4;
+        while (n2 < 2 * m2) n2 *= 2;
+        rows_too_long = lds_rows(n2, D) > kLdsHard;
+    }
+    if (D > RL_MAX_D || rows_too_long) {
         // wide operator: see rl_gridop::wide
         if (D > 4096) return fail(RL_ELIMIT, "rl_gridop_create: D > 4096 outputs not supported");
         rl_gridop* w = new rl_gridop;

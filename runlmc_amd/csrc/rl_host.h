@@ -162,6 +162,8 @@ struct rl_gridop {
     // whatever form that top takes) and k_wide_mix applies the dense couplings,
     //   Y[v][a] (+)= sum_b B_q[a][b] (T_q X)[v][b].
     // (reference kronecker.py:39-46 has no limit on D; Q products + Q mix passes)
+    // A 2-D grid with D <= RL_MAX_D whose row tile of D outputs exceeds the LDS takes the
+    // same route (gridop_create_impl: rows_too_long).
     bool wide = false;
     rl_gridop* child = nullptr;
     double* wide_B = nullptr;   // [max_tops][D][D]

@@ -1408,7 +1408,11 @@ static int dz_available(rl_ski* s, bool* ok, const char** why) {
     *ok = false;
     *why = "";
     if (!s->extra.empty()) { *why = "kernels on several grids"; return RL_OK; }
-    if (g->wide) { *why = "more than 16 outputs"; return RL_OK; }
+    if (g->wide) {
+        *why = g->D > RL_MAX_D ? "more than 16 outputs"
+                               : "2-D grid whose rows of D outputs exceed the LDS row tile";
+        return RL_OK;
+    }
     if (s->W4_base == nullptr || s->h_base.empty() || s->ngrid != g->D * g->m) {
         *why = "W is not a cubic interpolant of a 1-D grid"; return RL_OK;
     }
