@@ -45,7 +45,8 @@ typedef struct rl_exact rl_exact;
  * and rl_row_dots, the tiled predictive variances; 7: rl_sampler_*, rl_normal_fill and
  * rl_pathwise_residual, the function draws; 8: rl_ski_inverse_diag, rl_ski_precond_apply,
  * rl_diag_accumulate and rl_loo_reduce, leave-one-out cross-validation; callers
- * built against an older version must be rebuilt).  A binding
+ * built against an older version must be rebuilt; rl_exact_set_factors joined version 8
+ * without a bump: no declared signature changed).  A binding
  * compares rl_abi_version() with the RL_ABI_VERSION it was written against before its
  * first call (runlmc_amd/_lib.py does) instead of finding out through shifted arguments. */
 #define RL_ABI_VERSION 8
@@ -398,6 +399,25 @@ int rl_exact_destroy(rl_exact* h);
  * slots of rl_exact_grad_sums.                                                                  */
 int rl_exact_set(rl_exact* h, const double* X, const int* lens, int D, int Q, const int* kinds,
                  const double* params, const int* active_cols, const double* B, const double* noise);
+/* The same with every latent kernel a product  c prod_{f < nfact[q]} k_f(r)  of 1 .. 3 leaf
+ * kernels on ONE distance over the kernel's active columns (runlmc_amd/kern/stationary.py:
+ * Product, Cosine; the reference has neither):
+ *   nfact host [Q] (1 .. RL_EXACT_MAX_FACT); leaf_kinds host [Q][3]: RL_EXACT_RBF .. RL_EXACT_COSINE
+ *   (no RL_EXACT_SCALED here); leaf_params host [Q][3][2]: a leaf's parameters as listed above;
+ *   scaled host [Q] (0 / 1) and scales host [Q]: the factor c, a parameter when scaled[q];
+ *   entries of factors f >= nfact[q] are not read.  X, lens, active_cols, B, noise as above.
+ * Derivative order of kernel q (the slots of rl_exact_grad_sums): the factors in order, each
+ * factor's parameters in its own order (product rule: dk_f / dtheta_p prod_{g != f} k_g, times c),
+ * then the scale's (prod_f k_f): at most 2 * 3 + 1 = 7, and Q + sum_q p_q <= 32 as above
+ * (RL_ELIMIT, the message names the count).  RL_EINVAL: an unknown leaf kind, nfact outside
+ * 1 .. 3.  A one-factor list computes what rl_exact_set computes, bit for bit; every later call
+ * works unchanged in the state either call leaves.                                             */
+#define RL_EXACT_COSINE 4       /* cos(2 pi f r)               params [f]   (a leaf of rl_exact_set_factors only) */
+#define RL_EXACT_MAX_FACT 3
+int rl_exact_set_factors(rl_exact* h, const double* X, const int* lens, int D, int Q,
+                         const int* nfact, const int* leaf_kinds, const double* leaf_params,
+                         const int* scaled, const double* scales, const int* active_cols,
+                         const double* B, const double* noise);
 /* K into the device buffer (lower triangle; rl_exact_factor does it when needed). */
 int rl_exact_assemble(rl_exact* h);
 /* Blocked Cholesky K = L L^T in place (cho_factor, likelihood.py:153) and

@@ -573,6 +573,16 @@ RL_EXACT_SCALED = 16
 EXACT_MAX_COLS = 4
 
 
+def _exact_cols(k):
+    ad = list(k.active_dims)
+    if not ad:
+        raise ValueError('kernel %s has no active dimensions' % k.name)
+    if len(ad) > EXACT_MAX_COLS:
+        raise NotImplementedError('the exact likelihood takes kernels on at most %d input '
+                                  'dimensions, %s has %d' % (EXACT_MAX_COLS, k.name, len(ad)))
+    return ad + [-1] * (EXACT_MAX_COLS - len(ad))
+
+
 def exact_descriptors(kernels):
     """(kinds [Q], params [Q, 4], active columns [Q, 4], parameters per kernel) of the package's
     kernels for rl_exact_set.  A kernel class without a device formula raises
@@ -589,17 +599,70 @@ def exact_descriptors(kernels):
         kind = base[type(inner)] | (RL_EXACT_SCALED if scaled else 0)
         period = inner.period if type(inner) is StdPeriodic else 0.0
         params.append([inner.inv_lengthscale, period, k.scale if scaled else 0.0, 0.0])
-        ad = list(k.active_dims)
-        if not ad:
-            raise ValueError('kernel %s has no active dimensions' % k.name)
-        if len(ad) > EXACT_MAX_COLS:
-            raise NotImplementedError('the exact likelihood takes kernels on at most %d input '
-                                      'dimensions, %s has %d' % (EXACT_MAX_COLS, k.name, len(ad)))
-        cols.append(ad + [-1] * (EXACT_MAX_COLS - len(ad)))
+        cols.append(_exact_cols(k))
         kinds.append(kind)
         nder.append((2 if kind & 15 == 2 else 1) + (1 if scaled else 0))
     return (np.array(kinds, dtype=np.int32), np.array(params, dtype=np.float64),
             np.array(cols, dtype=np.int32), nder)
+
+
+EXACT_MAX_FACT = 3
+_EXACT_LEAVES = None
+
+
+def _exact_leaf_codes():
+    global _EXACT_LEAVES
+    if _EXACT_LEAVES is None:
+        from .kern.stationary import RBF, Matern32, Matern52, StdPeriodic, Cosine
+        _EXACT_LEAVES = {RBF: 0, Matern32: 1, StdPeriodic: 2, Matern52: 3, Cosine: 4}
+    return _EXACT_LEAVES
+
+
+def exact_is_composite(kernels):
+    """Whether a kernel set needs rl_exact_set_factors: a Product or a Cosine anywhere in it."""
+    from .kern.stationary import Cosine, Product, Scaled
+    inner = [k.k if type(k) is Scaled else k for k in kernels]
+    return any(type(k) in (Product, Cosine) for k in inner)
+
+
+def exact_factor_descriptors(kernels):
+    """(factors per kernel [Q], leaf kinds [Q, 3], leaf parameters [Q, 3, 2], scale flags [Q],
+    scales [Q], active columns [Q, 4], parameters per kernel) for rl_exact_set_factors: every
+    kernel a (Scaled) leaf or Product of leaves.  Derivatives per kernel: the factors' parameters
+    in order, the scale's last.  A class without a device formula raises NotImplementedError
+    naming it."""
+    from .kern.stationary import Cosine, Product, Scaled, StdPeriodic
+    codes = _exact_leaf_codes()
+    Q = len(kernels)
+    nfact = np.zeros(Q, dtype=np.int32)
+    leaves = np.zeros((Q, EXACT_MAX_FACT), dtype=np.int32)
+    params = np.zeros((Q, EXACT_MAX_FACT, 2), dtype=np.float64)
+    scaled = np.zeros(Q, dtype=np.int32)
+    scales = np.zeros(Q, dtype=np.float64)
+    cols, nder = [], []
+    for q, k in enumerate(kernels):
+        inner = k.k if type(k) is Scaled else k
+        factors = inner.factors if type(inner) is Product else [inner]
+        if len(factors) > EXACT_MAX_FACT:
+            raise NotImplementedError('the exact likelihood takes products of at most %d factors, '
+                                      '%s has %d' % (EXACT_MAX_FACT, k.name, len(factors)))
+        for f, leaf in enumerate(factors):
+            if type(leaf) not in codes:
+                raise NotImplementedError(
+                    'the exact likelihood has no device kernel for %s' % type(leaf).__name__)
+            leaves[q, f] = codes[type(leaf)]
+            if type(leaf) is Cosine:
+                params[q, f, 0] = leaf.frequency
+            else:
+                params[q, f, 0] = leaf.inv_lengthscale
+            if type(leaf) is StdPeriodic:
+                params[q, f, 1] = leaf.period
+        nfact[q] = len(factors)
+        if type(k) is Scaled:
+            scaled[q], scales[q] = 1, k.scale
+        cols.append(_exact_cols(k))
+        nder.append(sum(2 if type(leaf) is StdPeriodic else 1 for leaf in factors) + int(scaled[q]))
+    return nfact, leaves, params, scaled, scales, np.array(cols, dtype=np.int32), nder
 
 
 class ExactOp:
@@ -636,8 +699,14 @@ class ExactOp:
 
     def set(self, X, lens, kernels, coreg_mats, noise):
         """Data X (n, P) with rows the outputs concatenated, `lens` per output, the kernels
-        (runlmc_amd.kern), B_q (Q, D, D) and the noise (D,) -- rl_exact_set."""
-        kinds, params, cols, nder = exact_descriptors(kernels)
+        (runlmc_amd.kern), B_q (Q, D, D) and the noise (D,) -- rl_exact_set, or
+        rl_exact_set_factors when the set holds a Product or a Cosine."""
+        composite = exact_is_composite(kernels)
+        if composite:
+            nfact, leaves, lparams, scaled, scales, cols, nder = exact_factor_descriptors(kernels)
+            kinds = nfact
+        else:
+            kinds, params, cols, nder = exact_descriptors(kernels)
         B = as_f64(np.asarray(coreg_mats, dtype=np.float64))
         D = int(np.size(lens))
         if B.shape != (len(kinds), D, D):
@@ -650,8 +719,13 @@ class ExactOp:
         X, lens = self._rows(X, lens, 'rl_exact_set')
         if X.shape[0] != self.n:
             raise ValueError('the handle holds %d points, got %d' % (self.n, X.shape[0]))
-        self.lib.call('rl_exact_set', self._h, host_ptr(X), host_ptr(lens), D, len(kinds),
-                      host_ptr(kinds), host_ptr(params), host_ptr(cols), host_ptr(B), host_ptr(noise))
+        if composite:
+            self.lib.call('rl_exact_set_factors', self._h, host_ptr(X), host_ptr(lens), D, len(kinds),
+                          host_ptr(nfact), host_ptr(leaves), host_ptr(lparams), host_ptr(scaled),
+                          host_ptr(scales), host_ptr(cols), host_ptr(B), host_ptr(noise))
+        else:
+            self.lib.call('rl_exact_set', self._h, host_ptr(X), host_ptr(lens), D, len(kinds),
+                          host_ptr(kinds), host_ptr(params), host_ptr(cols), host_ptr(B), host_ptr(noise))
         self.D, self.Q, self.nder = D, len(kinds), nder
 
     def assemble(self):

@@ -7,7 +7,9 @@
 //   - tiles of EX_T = 64 rows / columns; every offset is 64-bit (n^2 > 2^31 from n ~ 46 000);
 //   - one n x n buffer, plus O(n * 64) workspaces: n is bounded by free device memory;
 //   - kernel descriptors: at most EX_MAX_SLOT = 32 values of k_q and dk_q / dtheta_p in all
-//     (Q + sum_q p_q), EX_MAX_COLS = 4 active input columns per kernel, D <= EX_MAX_D = 64.
+//     (Q + sum_q p_q), EX_MAX_COLS = 4 active input columns per kernel, D <= EX_MAX_D = 64;
+//   - a latent kernel is c prod_f k_f(r) of 1 .. EX_MAX_FACT = 3 leaf kernels on one distance
+//     (ex_desc / ex_eval_fact below): at most 2 * 3 + 1 = 7 derivatives per kernel.
 //
 // k_ex_gemm is the one update every blocked step uses (trailing SYRK of the factorisation,
 // off-diagonal blocks of the triangular solves, L^-1 and L^-T L^-1): C (+)= s A B^T on 64 x 64
@@ -30,7 +32,10 @@
 #define EX_MATERN32 1
 #define EX_STDPERIODIC 2
 #define EX_MATERN52 3
+#define EX_COSINE 4                 // cos(2 pi f r), prm[0] = f: only as a factor (rl_exact_set_factors)
 #define EX_SCALED 16
+#define EX_MAX_FACT 3
+#define EX_PRM2 (4 * EX_MAX_SLOT)    // where the parameters of factors 1, 2 begin, see ex_desc
 
 #if !defined(RL_EMU)
 typedef double ex_d4 __attribute__((ext_vector_type(4)));
@@ -103,6 +108,101 @@ __device__ __host__ __forceinline__ int ex_nder(int kind) {
     return ((kind & 15) == EX_STDPERIODIC ? 2 : 1) + ((kind & EX_SCALED) ? 1 : 0);
 }
 
+// ---------------------------------------------------------------------------
+// The descriptor of one latent kernel c prod_{f < nf} k_f(r) on the device: an int
+//   leaf_0 | (scaled ? EX_SCALED : 0) | (nf - 1) << 5 | leaf_1 << 8 | leaf_2 << 12
+// with its parameters in two places of one array: prm[4 q ..] = [g_0, T_0, c, -], ex_eval's
+// own layout, and prm[EX_PRM2 + 4 q ..] = [g_1, T_1, g_2, T_2] (g: the leaf's first parameter,
+// T: a periodic leaf's period).  With one factor these are ex_eval's kind and prm.
+// ---------------------------------------------------------------------------
+__device__ __host__ __forceinline__ int ex_desc(const int* leaf, int nf, bool scaled) {
+    return leaf[0] | (scaled ? EX_SCALED : 0) | (nf - 1) << 5 | (nf > 1 ? leaf[1] << 8 : 0) |
+           (nf > 2 ? leaf[2] << 12 : 0);
+}
+__device__ __host__ __forceinline__ int ex_desc_nf(int desc) { return ((desc >> 5) & 3) + 1; }
+__device__ __host__ __forceinline__ int ex_desc_leaf(int desc, int f) {
+    return f == 0 ? desc & 15 : (desc >> (4 + 4 * f)) & 15;
+}
+__device__ __host__ __forceinline__ int ex_leaf_nder(int leaf) { return leaf == EX_STDPERIODIC ? 2 : 1; }
+// one leaf of a factor list: ex_eval's four, or the cosine (kept out of ex_eval: the kernels of
+// plain sets compile without it)
+__device__ __forceinline__ void ex_leaf(int leaf, const double* prm, double r, double v[4]) {
+    if (leaf == EX_COSINE) {
+        const double w = 6.283185307179586 * prm[0] * r;
+        v[0] = cos(w);
+        v[1] = -(6.283185307179586 * r) * sin(w);
+    } else {
+        ex_eval(leaf, prm, r, v);
+    }
+}
+// derivatives of a descriptor: the factors' parameters in order, then the scale
+__device__ __host__ __forceinline__ int ex_desc_nder(int desc) {
+    int np = (desc & EX_SCALED) ? 1 : 0;
+    for (int f = 0; f < ex_desc_nf(desc); ++f) np += ex_leaf_nder(ex_desc_leaf(desc, f));
+    return np;
+}
+
+// ---------------------------------------------------------------------------
+// Value and every derivative of c prod_f k_f(r) for a descriptor of at most NF factors, in
+// FIXED places (registers, no indexed array):
+//   v[0] = c prod_f k_f,   v[1 + 2 f + p] = c dk_f / dtheta_p prod_{g != f} k_g   (product rule),
+//   v[7] = prod_f k_f  (the scale's derivative; 0 without a scale).
+// Places of absent factors and parameters hold 0.  Every old leaf goes through ex_eval; an absent
+// factor counts as the exact constant 1, so a single factor keeps ex_eval's bits, the scale is
+// applied as ex_eval applies it, and a NaN leaf value (StdPeriodic's convention) stays NaN.
+// ---------------------------------------------------------------------------
+template <int NF>
+__device__ __forceinline__ void ex_eval_fact(int desc, const double* prm, int q, double r, double v[8]) {
+    const double* p0 = prm + 4 * q;
+    const double* p1 = prm + EX_PRM2 + 4 * q;
+    const int nf = ex_desc_nf(desc);
+    double k[NF], d[NF][2];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        k[f] = 1.0;
+        d[f][0] = 0.0;
+        d[f][1] = 0.0;
+        if (f < nf) {
+            const int leaf = ex_desc_leaf(desc, f);
+            double t[4];
+            ex_leaf(leaf, f == 0 ? p0 : p1 + 2 * (f - 1), r, t);
+            k[f] = t[0];
+            d[f][0] = t[1];
+            if (leaf == EX_STDPERIODIC) d[f][1] = t[2];
+        }
+    }
+    double val = k[0];
+#pragma unroll
+    for (int f = 1; f < NF; ++f) val = val * k[f];
+#pragma unroll
+    for (int p = 1; p < 8; ++p) v[p] = 0.0;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+        double others = 1.0;
+#pragma unroll
+        for (int g = 0; g < NF; ++g)
+            if (g != f) others = others * k[g];
+        v[1 + 2 * f] = d[f][0] * others;
+        v[2 + 2 * f] = d[f][1] * others;
+    }
+    v[0] = val;
+    if (desc & EX_SCALED) {
+        const double c = p0[2];
+        v[7] = val;
+#pragma unroll
+        for (int p = 1; p < 7; ++p) v[p] = c * v[p];
+        v[0] = c * val;
+    }
+}
+
+// the value alone (kernels of more than one factor; the <1> bodies call ex_eval themselves)
+template <int NF>
+__device__ __forceinline__ double ex_value(int desc, const double* prm, int q, double r) {
+    double v[8];
+    ex_eval_fact<NF>(desc, prm, q, r, v);
+    return v[0];
+}
+
 __device__ __forceinline__ double ex_dist(const double* xa, const double* xb, const int* cols) {
     double s = 0.0;
     for (int c = 0; c < EX_MAX_COLS; ++c) {
@@ -118,8 +218,10 @@ __device__ __forceinline__ double ex_dist(const double* xa, const double* xb, co
 // out[i][j] = sum_q B_q[oa(i), ob(j)] k_q(r_q(xa_i, xb_j))  (+ noise[oa(i)] where i + diag_off == j)
 // for i < nrows, j < ncols; lower != 0 skips tiles above the diagonal.  grid (ceil(ncols / 64),
 // ceil(nrows / 64)), block 256: a thread fills 16 entries of a 64 x 64 tile, rows of 64
-// consecutive columns per quarter of the block.
+// consecutive columns per quarter of the block.  NF: the most factors of any kernel of the
+// handle (1: plain kernels, ex_eval as it stands; EX_MAX_FACT otherwise).
 // ---------------------------------------------------------------------------
+template <int NF>
 __global__ void __launch_bounds__(256)
 k_ex_assemble(double* __restrict__ out, long long ldo, int nrows, int ncols,
               const double* __restrict__ Xa, const int* __restrict__ oa,
@@ -136,10 +238,14 @@ k_ex_assemble(double* __restrict__ out, long long ldo, int nrows, int ncols,
         const int a = oa[i], b = ob[j];
         double acc = 0.0;
         for (int q = 0; q < Q; ++q) {
-            double v[4];
             const double r = ex_dist(Xa + (long long)i * P, Xb + (long long)j * P, cols + q * EX_MAX_COLS);
-            ex_eval(kinds[q], prm + 4 * q, r, v);
-            acc += Bm[((long long)q * D + a) * D + b] * v[0];
+            if constexpr (NF == 1) {
+                double v[4];
+                ex_eval(kinds[q], prm + 4 * q, r, v);
+                acc += Bm[((long long)q * D + a) * D + b] * v[0];
+            } else {
+                acc += Bm[((long long)q * D + a) * D + b] * ex_value<NF>(kinds[q], prm, q, r);
+            }
         }
         if (noise && i + diag_off == j) acc += noise[a];
         out[(long long)i * ldo + j] = acc;
@@ -155,10 +261,11 @@ k_ex_assemble(double* __restrict__ out, long long ldo, int nrows, int ncols,
 // (leading dimension ldx, odd: neighbouring threads on other banks).  A thread owns column
 // j = blockIdx.x EX_CR_COLS + threadIdx.x: it reads x_j and ob(j) once, loops over the staged
 // rows and stores out[t][j], consecutive along j across the wave.  Every entry goes through
-// ex_dist / ex_eval with the sum over q in k_ex_assemble's order.
+// ex_dist / ex_eval (ex_value<NF> past one factor) with the sum over q in k_ex_assemble's order.
 // LDS: rg (P + Q D) + (stage_cols ? EX_CR_COLS ldx : 0) doubles (ex_cross_rows sizes rg).
 // ---------------------------------------------------------------------------
 #define EX_CR_COLS 256
+template <int NF>
 __global__ void __launch_bounds__(EX_CR_COLS)
 k_ex_cross_rows(double* __restrict__ out, long long ldo, int nrows, int ncols, int rg,
                 const double* __restrict__ Xt, const int* __restrict__ ot,
@@ -194,10 +301,14 @@ k_ex_cross_rows(double* __restrict__ out, long long ldo, int nrows, int ncols, i
         const double* bt = sb + (long long)t * QD + b;
         double acc = 0.0;
         for (int q = 0; q < Q; ++q) {
-            double v[4];
             const double r = ex_dist(xa, xb, cols + q * EX_MAX_COLS);
-            ex_eval(kinds[q], prm + 4 * q, r, v);
-            acc += bt[q * D] * v[0];
+            if constexpr (NF == 1) {
+                double v[4];
+                ex_eval(kinds[q], prm + 4 * q, r, v);
+                acc += bt[q * D] * v[0];
+            } else {
+                acc += bt[q * D] * ex_value<NF>(kinds[q], prm, q, r);
+            }
         }
         out[(long long)(t0 + t) * ldo + j] = acc;
     }
@@ -562,7 +673,11 @@ k_ex_sum2(const double* __restrict__ x, int n, double* __restrict__ out) {
 // M_ij dk_q / dtheta_p into slot dslot[q] + p, and M_ii into slot nslot (noise).  The
 // workgroup's nslot + 1 sums go to part[w][.] (fixed order: threads by index).
 // block 256, LDS (nslot + 1) x 256 doubles.
+// NF == 1 (plain kernels): up to three derivatives from ex_eval, four sums per thread.
+// NF > 1: ex_eval_fact's eight fixed places summed in eight registers, then stored to the slots
+// dslot[q] + p in the derivative order (factors in order, the scale last).
 // ---------------------------------------------------------------------------
+template <int NF>
 __global__ void __launch_bounds__(256)
 k_ex_grad_tiles(const double* __restrict__ Kinv, long long n, const double* __restrict__ alpha,
                 const int* __restrict__ tiles, const int* __restrict__ bounds,
@@ -593,25 +708,52 @@ k_ex_grad_tiles(const double* __restrict__ Kinv, long long n, const double* __re
         const int kind = kinds[q];
         const double* pq = prm + 4 * q;
         const int* cq = cols + q * EX_MAX_COLS;
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        int np = 0;
-        for (int u = 0; u < 16; ++u) {
-            const int e = tid + 256 * u;
-            const int i = r0 + e / EX_T, j = c0 + e % EX_T;
-            if (i >= re || j >= ce || (a == b && j > i)) continue;
-            double v[4];
-            np = ex_eval(kind, pq, ex_dist(X + (long long)i * P, X + (long long)j * P, cq), v);
-            const double m = mw[u];
-            s0 += m * v[0];
-            s1 += m * v[1];
-            if (np > 1) s2 += m * v[2];
-            if (np > 2) s3 += m * v[3];
+        if constexpr (NF == 1) {
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+            int np = 0;
+            for (int u = 0; u < 16; ++u) {
+                const int e = tid + 256 * u;
+                const int i = r0 + e / EX_T, j = c0 + e % EX_T;
+                if (i >= re || j >= ce || (a == b && j > i)) continue;
+                double v[4];
+                np = ex_eval(kind, pq, ex_dist(X + (long long)i * P, X + (long long)j * P, cq), v);
+                const double m = mw[u];
+                s0 += m * v[0];
+                s1 += m * v[1];
+                if (np > 1) s2 += m * v[2];
+                if (np > 2) s3 += m * v[3];
+            }
+            np = ex_nder(kind);       // (a thread without entries has summed zeros)
+            red[q * 256 + tid] = s0;
+            red[(dslot[q] + 0) * 256 + tid] = s1;
+            if (np > 1) red[(dslot[q] + 1) * 256 + tid] = s2;
+            if (np > 2) red[(dslot[q] + 2) * 256 + tid] = s3;
+        } else {
+            double s[8];
+#pragma unroll
+            for (int p = 0; p < 8; ++p) s[p] = 0.0;
+            for (int u = 0; u < 16; ++u) {
+                const int e = tid + 256 * u;
+                const int i = r0 + e / EX_T, j = c0 + e % EX_T;
+                if (i >= re || j >= ce || (a == b && j > i)) continue;
+                double v[8];
+                ex_eval_fact<NF>(kind, prm, q, ex_dist(X + (long long)i * P, X + (long long)j * P, cq), v);
+                const double m = mw[u];
+#pragma unroll
+                for (int p = 0; p < 8; ++p) s[p] += m * v[p];
+            }
+            red[q * 256 + tid] = s[0];
+            int slot = dslot[q];
+            const int nf = ex_desc_nf(kind);
+#pragma unroll
+            for (int f = 0; f < NF; ++f) {
+                if (f >= nf) continue;
+                red[slot * 256 + tid] = s[1 + 2 * f];
+                if (ex_leaf_nder(ex_desc_leaf(kind, f)) > 1) red[(slot + 1) * 256 + tid] = s[2 + 2 * f];
+                slot += ex_leaf_nder(ex_desc_leaf(kind, f));
+            }
+            if (kind & EX_SCALED) red[slot * 256 + tid] = s[7];
         }
-        np = ex_nder(kind);       // (a thread without entries has summed zeros)
-        red[q * 256 + tid] = s0;
-        red[(dslot[q] + 0) * 256 + tid] = s1;
-        if (np > 1) red[(dslot[q] + 1) * 256 + tid] = s2;
-        if (np > 2) red[(dslot[q] + 2) * 256 + tid] = s3;
     }
     __syncthreads();
     if (tid <= nslot) {

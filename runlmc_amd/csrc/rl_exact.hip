@@ -8,12 +8,13 @@ enum { EX_EMPTY = 0, EX_SET, EX_ASSEMBLED, EX_FACTORED, EX_INVERTED };
 
 struct rl_exact {
     int device = 0, n = 0, P = 0, D = 0, Q = 0, nslot = 0, ncu = 1;
+    int maxf = 1;                   // most factors of any kernel (3 with any cosine leaf): 1 runs the kernels' <1> bodies
     int state = EX_EMPTY;
     double* A = nullptr;            // n x n
     double* X = nullptr;            // n x P
     int* out_of = nullptr;          // n: output of each row
     int* bounds = nullptr;          // D + 1 row offsets of the outputs
-    int* kinds = nullptr;           // descriptors (capacity EX_MAX_SLOT kernels)
+    int* kinds = nullptr;           // descriptors (rl_exact.h: ex_desc; capacity EX_MAX_SLOT kernels)
     double* prm = nullptr;
     int* cols = nullptr;
     int* dslot = nullptr;
@@ -47,6 +48,15 @@ static int ex_ws(rl_exact* h, size_t doubles) {
     h->ws_cap = doubles;
     return RL_OK;
 }
+
+// a kernel templated on the factor count, at the handle's: plain sets run <1>
+#define EX_LAUNCH_FACT(h, kern, grid, block, smem, stream, ...)                         \
+    do {                                                                                \
+        if ((h)->maxf == 1)                                                             \
+            RL_LAUNCH(kern<1>, grid, block, smem, stream, __VA_ARGS__);                 \
+        else                                                                            \
+            RL_LAUNCH(kern<EX_MAX_FACT>, grid, block, smem, stream, __VA_ARGS__);       \
+    } while (0)
 
 static inline int ex_tiles(long long v) { return (int)((v + EX_T - 1) / EX_T); }
 static const size_t kGemmLds = 2 * EX_T * EX_LDK * sizeof(double);
@@ -123,7 +133,7 @@ static int ex_trsv(rl_exact* h, hipStream_t st, double* R, int nrhs, bool forwar
 static int ex_cross(rl_exact* h, hipStream_t st, double* out, const double* Xa, const int* oa,
                     int nrows, const double* noise, int diag_off) {
     if (nrows <= 0) return RL_OK;
-    RL_LAUNCH(k_ex_assemble, dim3(ex_tiles(h->n), ex_tiles(nrows)), dim3(256), 0, st, out,
+    EX_LAUNCH_FACT(h, k_ex_assemble, dim3(ex_tiles(h->n), ex_tiles(nrows)), dim3(256), 0, st, out,
               (long long)h->n, nrows, h->n, Xa, oa, (const double*)h->X, (const int*)h->out_of,
               h->P, h->Q, (const int*)h->kinds, (const double*)h->prm, (const int*)h->cols,
               (const double*)h->Bm, h->D, noise, diag_off, 0);
@@ -149,7 +159,7 @@ extern "C" int rl_exact_create(int device, int n, int P, rl_exact** out) {
     RL_HIP(hipMalloc((void**)&h->out_of, (size_t)n * sizeof(int)));
     RL_HIP(hipMalloc((void**)&h->bounds, (EX_MAX_D + 1) * sizeof(int)));
     RL_HIP(hipMalloc((void**)&h->kinds, EX_MAX_SLOT * sizeof(int)));
-    RL_HIP(hipMalloc((void**)&h->prm, EX_MAX_SLOT * 4 * sizeof(double)));
+    RL_HIP(hipMalloc((void**)&h->prm, 2 * EX_PRM2 * sizeof(double)));
     RL_HIP(hipMalloc((void**)&h->cols, EX_MAX_SLOT * EX_MAX_COLS * sizeof(int)));
     RL_HIP(hipMalloc((void**)&h->dslot, EX_MAX_SLOT * sizeof(int)));
     RL_HIP(hipMalloc((void**)&h->Bm, (size_t)EX_MAX_SLOT * EX_MAX_D * EX_MAX_D * sizeof(double)));
@@ -159,7 +169,10 @@ extern "C" int rl_exact_create(int device, int n, int P, rl_exact** out) {
     RL_HIP(hipMalloc((void**)&h->flag, sizeof(int)));
     RL_HIP(hipMalloc((void**)&h->gout,
                      ((size_t)EX_MAX_SLOT * EX_MAX_D * EX_MAX_D + EX_MAX_D) * sizeof(double)));
-    (void)hipFuncSetAttribute((const void*)k_ex_grad_tiles,
+    (void)hipFuncSetAttribute((const void*)k_ex_grad_tiles<1>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (EX_MAX_SLOT + 1) * 256 * (int)sizeof(double));
+    (void)hipFuncSetAttribute((const void*)k_ex_grad_tiles<EX_MAX_FACT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize,
                               (EX_MAX_SLOT + 1) * 256 * (int)sizeof(double));
     *out = guard.release();
@@ -178,41 +191,60 @@ extern "C" int rl_exact_destroy(rl_exact* h) {
     return RL_OK;
 }
 
-extern "C" int rl_exact_set(rl_exact* h, const double* X, const int* lens, int D, int Q,
-                            const int* kinds, const double* params, const int* active_cols,
-                            const double* B, const double* noise) {
-    if (!h || !X || !lens || !kinds || !params || !active_cols || !B || !noise)
-        return fail(RL_EINVAL, "rl_exact_set: NULL argument");
-    if (D < 1 || Q < 1) return fail(RL_EINVAL, "rl_exact_set: D and Q must be >= 1");
-    if (D > EX_MAX_D) return fail(RL_ELIMIT, "rl_exact_set: D > 64 outputs");
+// What rl_exact_set and rl_exact_set_factors share.  `describe(q, desc, p0, p1)` validates kernel q
+// of the caller's arguments and writes its device descriptor (rl_exact.h: ex_desc) and its two
+// parameter groups, [g_0, T_0, c, -] and [g_1, T_1, g_2, T_2]; it runs per kernel where
+// rl_exact_set has always checked the kind, so every error keeps its precedence.  Nothing indexed
+// by q is written past EX_MAX_SLOT kernels: a larger Q only counts, and is refused with the count.
+// `what` names the entry point in messages.
+template <class Describe>
+static int ex_set(rl_exact* h, const char* what, const double* X, const int* lens, int D, int Q,
+                  Describe describe, const int* active_cols, const double* B, const double* noise) {
+    const std::string fn = what;
+    if (D > EX_MAX_D) return fail(RL_ELIMIT, fn + ": D > 64 outputs");
     long long total = 0;
     for (int d = 0; d < D; ++d) {
-        if (lens[d] < 0) return fail(RL_EINVAL, "rl_exact_set: negative output length");
+        if (lens[d] < 0) return fail(RL_EINVAL, fn + ": negative output length");
         total += lens[d];
     }
     if (total != h->n)
-        return fail(RL_EINVAL, "rl_exact_set: lens sum to " + std::to_string(total) + ", handle has n = " +
+        return fail(RL_EINVAL, fn + ": lens sum to " + std::to_string(total) + ", handle has n = " +
                                    std::to_string(h->n));
-    int nslot = Q;
-    std::vector<int> dslot(Q), cols((size_t)Q * EX_MAX_COLS);
+    long long nslot = Q;
+    int maxf = 1;
+    std::vector<int> descs(EX_MAX_SLOT, 0), dslot(EX_MAX_SLOT, 0), cols((size_t)EX_MAX_SLOT * EX_MAX_COLS, -1);
+    std::vector<double> prm(2 * EX_PRM2, 0.0);
     for (int q = 0; q < Q; ++q) {
-        const int base = kinds[q] & ~EX_SCALED;
-        if (base != EX_RBF && base != EX_MATERN32 && base != EX_STDPERIODIC && base != EX_MATERN52)
-            return fail(RL_EINVAL, "rl_exact_set: unknown kernel kind " + std::to_string(kinds[q]));
-        dslot[q] = nslot;
-        nslot += ex_nder(kinds[q]);
+        int desc = 0;
+        double p0[4] = {0.0, 0.0, 0.0, 0.0}, p1[4] = {0.0, 0.0, 0.0, 0.0};
+        RL_TRY(describe(q, &desc, p0, p1));
+        const int slot = (int)std::min<long long>(nslot, EX_MAX_SLOT);
+        nslot += ex_desc_nder(desc);
+        maxf = std::max(maxf, ex_desc_nf(desc));
+        // (a cosine leaf has no formula in ex_eval: even alone it runs the factor-list bodies)
+        if (ex_desc_leaf(desc, 0) == EX_COSINE) maxf = EX_MAX_FACT;
+        const bool keep = q < EX_MAX_SLOT;
+        if (keep) {
+            descs[q] = desc;
+            dslot[q] = slot;
+            for (int p = 0; p < 4; ++p) {
+                prm[4 * q + p] = p0[p];
+                prm[EX_PRM2 + 4 * q + p] = p1[p];
+            }
+        }
         int nc = 0;
         for (int c = 0; c < EX_MAX_COLS; ++c) {
             const int col = active_cols[q * EX_MAX_COLS + c];
-            if (col >= h->P) return fail(RL_EINVAL, "rl_exact_set: active column beyond P");
+            if (col >= h->P) return fail(RL_EINVAL, fn + ": active column beyond P");
             if (col < 0) break;
             ++nc;
         }
-        if (nc == 0) return fail(RL_EINVAL, "rl_exact_set: a kernel without active columns");
-        for (int c = 0; c < EX_MAX_COLS; ++c) cols[q * EX_MAX_COLS + c] = c < nc ? active_cols[q * EX_MAX_COLS + c] : -1;
+        if (nc == 0) return fail(RL_EINVAL, fn + ": a kernel without active columns");
+        if (keep)
+            for (int c = 0; c < EX_MAX_COLS; ++c) cols[q * EX_MAX_COLS + c] = c < nc ? active_cols[q * EX_MAX_COLS + c] : -1;
     }
     if (nslot > EX_MAX_SLOT)
-        return fail(RL_ELIMIT, "rl_exact_set: Q + sum of kernel parameters = " + std::to_string(nslot) +
+        return fail(RL_ELIMIT, fn + ": Q + sum of kernel parameters = " + std::to_string(nslot) +
                                    " > 32");
     RL_HIP(hipSetDevice(h->device));
     std::vector<int> out_of(h->n), bounds(D + 1, 0);
@@ -223,9 +255,9 @@ extern "C" int rl_exact_set(rl_exact* h, const double* X, const int* lens, int D
     RL_HIP(hipMemcpy(h->X, X, (size_t)h->n * h->P * sizeof(double), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(h->out_of, out_of.data(), (size_t)h->n * sizeof(int), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(h->bounds, bounds.data(), (D + 1) * sizeof(int), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(h->kinds, kinds, Q * sizeof(int), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(h->prm, params, (size_t)Q * 4 * sizeof(double), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(h->cols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->kinds, descs.data(), Q * sizeof(int), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->prm, prm.data(), 2 * EX_PRM2 * sizeof(double), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->cols, cols.data(), (size_t)Q * EX_MAX_COLS * sizeof(int), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(h->dslot, dslot.data(), Q * sizeof(int), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(h->Bm, B, (size_t)Q * D * D * sizeof(double), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(h->noise, noise, D * sizeof(double), hipMemcpyHostToDevice));
@@ -252,10 +284,58 @@ extern "C" int rl_exact_set(rl_exact* h, const double* X, const int* lens, int D
     }
     h->D = D;
     h->Q = Q;
-    h->nslot = nslot;
+    h->nslot = (int)nslot;
+    h->maxf = maxf;
     h->hbounds = bounds;
     h->state = EX_SET;
     return RL_OK;
+}
+
+extern "C" int rl_exact_set(rl_exact* h, const double* X, const int* lens, int D, int Q,
+                            const int* kinds, const double* params, const int* active_cols,
+                            const double* B, const double* noise) {
+    if (!h || !X || !lens || !kinds || !params || !active_cols || !B || !noise)
+        return fail(RL_EINVAL, "rl_exact_set: NULL argument");
+    if (D < 1 || Q < 1) return fail(RL_EINVAL, "rl_exact_set: D and Q must be >= 1");
+    auto describe = [&](int q, int* desc, double* p0, double*) -> int {
+        const int base = kinds[q] & ~EX_SCALED;
+        if (base != EX_RBF && base != EX_MATERN32 && base != EX_STDPERIODIC && base != EX_MATERN52)
+            return fail(RL_EINVAL, "rl_exact_set: unknown kernel kind " + std::to_string(kinds[q]));
+        *desc = kinds[q];
+        for (int p = 0; p < 4; ++p) p0[p] = params[q * 4 + p];
+        return RL_OK;
+    };
+    return ex_set(h, "rl_exact_set", X, lens, D, Q, describe, active_cols, B, noise);
+}
+
+extern "C" int rl_exact_set_factors(rl_exact* h, const double* X, const int* lens, int D, int Q,
+                                    const int* nfact, const int* leaf_kinds,
+                                    const double* leaf_params, const int* scaled,
+                                    const double* scales, const int* active_cols, const double* B,
+                                    const double* noise) {
+    if (!h || !X || !lens || !nfact || !leaf_kinds || !leaf_params || !scaled || !scales ||
+        !active_cols || !B || !noise)
+        return fail(RL_EINVAL, "rl_exact_set_factors: NULL argument");
+    if (D < 1 || Q < 1) return fail(RL_EINVAL, "rl_exact_set_factors: D and Q must be >= 1");
+    auto describe = [&](int q, int* desc, double* p0, double* p1) -> int {
+        const int nf = nfact[q];
+        if (nf < 1 || nf > EX_MAX_FACT)
+            return fail(RL_EINVAL, "rl_exact_set_factors: kernel " + std::to_string(q) + " has " +
+                                       std::to_string(nf) + " factors (1 .. 3)");
+        const int* leaf = leaf_kinds + (size_t)q * EX_MAX_FACT;
+        for (int f = 0; f < nf; ++f) {
+            if (leaf[f] != EX_RBF && leaf[f] != EX_MATERN32 && leaf[f] != EX_STDPERIODIC &&
+                leaf[f] != EX_MATERN52 && leaf[f] != EX_COSINE)
+                return fail(RL_EINVAL, "rl_exact_set_factors: unknown kernel kind " + std::to_string(leaf[f]));
+            double* pf = f == 0 ? p0 : p1 + 2 * (f - 1);
+            pf[0] = leaf_params[((size_t)q * EX_MAX_FACT + f) * 2];
+            pf[1] = leaf_params[((size_t)q * EX_MAX_FACT + f) * 2 + 1];
+        }
+        p0[2] = scaled[q] ? scales[q] : 0.0;
+        *desc = ex_desc(leaf, nf, scaled[q] != 0);
+        return RL_OK;
+    };
+    return ex_set(h, "rl_exact_set_factors", X, lens, D, Q, describe, active_cols, B, noise);
 }
 
 extern "C" int rl_exact_assemble(rl_exact* h) {
@@ -278,7 +358,7 @@ extern "C" int rl_exact_assemble(rl_exact* h) {
         }
     }
     const int nb = ex_tiles(n);
-    RL_LAUNCH(k_ex_assemble, dim3(nb, nb), dim3(256), 0, (hipStream_t)0, h->A, (long long)n, n, n,
+    EX_LAUNCH_FACT(h, k_ex_assemble, dim3(nb, nb), dim3(256), 0, (hipStream_t)0, h->A, (long long)n, n, n,
               (const double*)h->X, (const int*)h->out_of, (const double*)h->X,
               (const int*)h->out_of, h->P, h->Q, (const int*)h->kinds, (const double*)h->prm,
               (const int*)h->cols, (const double*)h->Bm, h->D, (const double*)h->noise, 0, 1);
@@ -496,7 +576,7 @@ extern "C" int rl_exact_cross_dev(rl_exact* h, const double* Xtest, const int* t
     const long long gx = ((long long)h->n + EX_CR_COLS - 1) / EX_CR_COLS;
     const int gy = (nrows + rg - 1) / rg;
     if (gy > 65535) return fail(RL_ELIMIT, "rl_exact_cross_dev: too many row groups in one call");
-    RL_LAUNCH(k_ex_cross_rows, dim3((unsigned)gx, (unsigned)gy), dim3(EX_CR_COLS), lds, st, out,
+    EX_LAUNCH_FACT(h, k_ex_cross_rows, dim3((unsigned)gx, (unsigned)gy), dim3(EX_CR_COLS), lds, st, out,
               (long long)h->n, nrows, h->n, rg, (const double*)h->xt, (const int*)h->ot,
               (const double*)h->X, (const int*)h->out_of, P, Q, (const int*)h->kinds,
               (const double*)h->prm, (const int*)h->cols, (const double*)h->Bm, D, stage_cols, ldx);
@@ -572,7 +652,7 @@ extern "C" int rl_exact_grad_sums(rl_exact* h, const double* alpha, double* out)
     RL_HIP(hipMemsetAsync(h->gout, 0, nout * sizeof(double), st));
     if (h->ntiles > 0) {
         RL_TRY(ex_ws(h, (size_t)h->ntiles * (ns + 1)));
-        RL_LAUNCH(k_ex_grad_tiles, dim3(h->ntiles), dim3(256), (size_t)(ns + 1) * 256 * sizeof(double),
+        EX_LAUNCH_FACT(h, k_ex_grad_tiles, dim3(h->ntiles), dim3(256), (size_t)(ns + 1) * 256 * sizeof(double),
                   st, (const double*)h->A, (long long)h->n, alpha, (const int*)h->tiles,
                   (const int*)h->bounds, (const double*)h->X, h->P, h->Q, (const int*)h->kinds,
                   (const double*)h->prm, (const int*)h->cols, (const int*)h->dslot, ns, h->ws);

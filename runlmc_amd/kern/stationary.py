@@ -163,3 +163,111 @@ class Scaled(StationaryKern):
 
     def set_params(self, p):
         self.k.set_params(p)
+
+
+class Cosine(StationaryKern):
+    """cos(2 pi f r): a rank-2 positive semidefinite kernel (the reference has none); as a
+    factor of a Product it makes a spectral-mixture component or a damped cosine."""
+
+    def __init__(self, frequency=1, name='cosine', active_dims=None):
+        super().__init__(name, active_dims)
+        self.frequency = float(frequency)
+
+    def from_dist(self, dists):
+        return np.cos(2 * np.pi * self.frequency * dists)
+
+    def kernel_gradient(self, dists):
+        return [-(2 * np.pi * dists) * np.sin(2 * np.pi * self.frequency * dists)]
+
+    @property
+    def param_array(self):
+        return np.array([self.frequency])
+
+    def set_params(self, p):
+        self.frequency = float(p[0])
+
+
+class Product(StationaryKern):
+    """k_1(r) k_2(r) [k_3(r)]: 2 or 3 leaf kernels (RBF, Matern32, Matern52, StdPeriodic,
+    Cosine) on ONE Euclidean distance over the product's active dimensions.  Parameters and
+    derivatives: the factors in the order given, each factor's in its own order.  A scale goes
+    outside: Scaled(Product(...), c)."""
+
+    MAX_FACTORS = 3
+
+    def __init__(self, *factors, name=None, active_dims=None):
+        leaves = []
+        for f in factors:
+            if isinstance(f, Scaled):
+                raise ValueError('a Scaled factor in a Product: put the scale outside, '
+                                 'Scaled(Product(...), c)')
+            if isinstance(f, Product):
+                leaves.extend(f.factors)
+            elif type(f) in (RBF, Matern32, Matern52, StdPeriodic, Cosine):
+                leaves.append(f)
+            else:
+                raise ValueError('a Product takes RBF, Matern32, Matern52, StdPeriodic and Cosine '
+                                 'factors, got %s' % type(f).__name__)
+        if len(leaves) < 2:
+            raise ValueError('a Product takes at least 2 factors, got %d' % len(leaves))
+        if len(leaves) > self.MAX_FACTORS:
+            raise ValueError('a Product takes at most %d leaf factors, got %d'
+                             % (self.MAX_FACTORS, len(leaves)))
+        want = None if active_dims is None else tuple(sorted(active_dims))
+        for f in leaves:
+            if f.active_dims is not None and tuple(sorted(f.active_dims)) != want:
+                raise ValueError('factor %s acts on dimensions %s, the product on %s: every factor '
+                                 'takes the product\'s distance' % (f.name, f.active_dims, active_dims))
+        self.factors = leaves
+        super().__init__(name or '_x_'.join(f.name for f in leaves), active_dims)
+
+    @property
+    def active_dims(self):
+        return self._active_dims
+
+    @active_dims.setter
+    def active_dims(self, value):
+        self._active_dims = value
+        for f in self.factors:
+            f.active_dims = value
+
+    def from_dist(self, dists):
+        vals = [f.from_dist(dists) for f in self.factors]
+        if any(np.ndim(v) == 0 and np.isnan(v) for v in vals):
+            return np.nan       # (StdPeriodic's convention for a vanishing period)
+        out = vals[0]
+        for v in vals[1:]:
+            out = out * v
+        return out
+
+    def kernel_gradient(self, dists):
+        vals = [f.from_dist(dists) for f in self.factors]
+        grads = []
+        for i, f in enumerate(self.factors):
+            others = 1.0
+            for j, v in enumerate(vals):
+                if j != i:
+                    others = others * v
+            grads.extend(g * others for g in f.kernel_gradient(dists))
+        return grads
+
+    def _sizes(self):
+        return [len(f.param_array) for f in self.factors]
+
+    def update_gradient(self, grad):
+        grad = np.asarray(grad, dtype=float)
+        self.gradient = grad
+        pos = 0
+        for f, n in zip(self.factors, self._sizes()):
+            f.update_gradient(grad[pos:pos + n])
+            pos += n
+
+    @property
+    def param_array(self):
+        return np.concatenate([f.param_array for f in self.factors])
+
+    def set_params(self, p):
+        pos = 0
+        for f, n in zip(self.factors, self._sizes()):
+            f.set_params(p[pos:pos + n])
+            pos += n
