@@ -44,24 +44,52 @@ typedef const double __attribute__((address_space(4)))* rl_kconst;
 // < 2^31): a buffer access -- the base lives in scalar registers, ONE offset register serves
 // every access of a loop over bases, and an offset at or past `nbytes` reads 0 / stores
 // nothing (the hardware's range check: no clamped index, no masked store).
+// POL is the cache policy of the access, the intrinsic's last argument as gfx950 encodes it:
+// plain, `nt` (streaming: the line is the first to go and displaces no dirty one), `sc1` (a store
+// that writes through and leaves no line in the L2).  A hint only: the emulator ignores it.
+#define RL_POL_PLAIN 0
+#define RL_POL_NT 2
+#define RL_POL_SC1 16
 #if defined(RL_EMU)
+template <int POL = RL_POL_PLAIN>
 __device__ __forceinline__ double rl_row_load(const double* base, unsigned nbytes, unsigned off) {
     return off < nbytes ? *reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + off) : 0.0;
 }
+template <int POL = RL_POL_PLAIN>
 __device__ __forceinline__ void rl_row_store(double* base, unsigned nbytes, unsigned off, double v) {
     if (off < nbytes) *reinterpret_cast<double*>(reinterpret_cast<char*>(base) + off) = v;
 }
+// the same two policies on a plain pointer (plain or `nt`)
+template <int POL>
+__device__ __forceinline__ double rl_ptr_load(const double* p) { return *p; }
+template <int POL>
+__device__ __forceinline__ void rl_ptr_store(double* p, double v) { *p = v; }
 #else
 typedef unsigned int rl_u32x2 __attribute__((ext_vector_type(2)));
 #define RL_BUFFER_WORD3 0x00020000       // raw buffer, 32-bit data format (gfx90a .. gfx950)
+template <int POL = RL_POL_PLAIN>
 __device__ __forceinline__ double rl_row_load(const double* base, unsigned nbytes, unsigned off) {
     const __amdgpu_buffer_rsrc_t r =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(base), 0, (int)nbytes, RL_BUFFER_WORD3);
-    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, 0));
+    return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (int)off, 0, POL));
 }
+template <int POL = RL_POL_PLAIN>
 __device__ __forceinline__ void rl_row_store(double* base, unsigned nbytes, unsigned off, double v) {
     const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)nbytes, RL_BUFFER_WORD3);
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(rl_u32x2, v), r, (int)off, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(rl_u32x2, v), r, (int)off, 0, POL);
+}
+// the same two policies on a plain pointer (plain or `nt`)
+template <int POL>
+__device__ __forceinline__ double rl_ptr_load(const double* p) {
+    static_assert(POL == RL_POL_PLAIN || POL == RL_POL_NT, "a plain pointer takes plain or nt");
+    if constexpr (POL == RL_POL_NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+template <int POL>
+__device__ __forceinline__ void rl_ptr_store(double* p, double v) {
+    static_assert(POL == RL_POL_PLAIN || POL == RL_POL_NT, "a plain pointer takes plain or nt");
+    if constexpr (POL == RL_POL_NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
 }
 #endif
 

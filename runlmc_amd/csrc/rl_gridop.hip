@@ -99,6 +99,13 @@ RlKnobs read_knobs() {
     k.rp_stagger = (int)num("RUNLMC_RP_STAGGER", 7);
     k.no_lr_small = flag("RUNLMC_NO_LR_SMALL");
     k.lr_expand_plain = (int)num("RUNLMC_LR_EXPAND_PLAIN", 0);
+    k.lr_policy = (int)num("RUNLMC_LR_POLICY", -1);
+    if (k.lr_policy < 0) {
+        k.lr_policy = -1;
+    } else if (k.lr_policy > RL_LR_POLICY_MAX || ((k.lr_policy >> 1) & 3) == 3) {
+        fprintf(stderr, "runlmc_hip: RUNLMC_LR_POLICY=%d names no policy and is ignored\n", k.lr_policy);
+        k.lr_policy = -1;
+    }
     k.no_precond_approx = flag("RUNLMC_NO_PRECOND_APPROX");
     k.no_precond_hi = flag("RUNLMC_NO_PRECOND_HI");
     k.precond_hi_passes = flag("RUNLMC_PRECOND_HI_PASSES");
@@ -1374,12 +1381,15 @@ static size_t lr_min_elements(const rl_gridop* g) {
 // launches the projection, returns the number of chunks (partial sums per row)
 template <int R>
 static int lr_project(rl_gridop* g, const double* X, int nrows, hipStream_t st,
-                      double* part = nullptr) {
+                      double* part = nullptr, bool measured = false) {
+    // (`measured`: the call is the projection of a product the policy's default was measured on
+    // -- lr_launch, not accumulating; every other call site takes a policy from the knob only)
     const int steps = lr_steps(g, nrows, R);
     const int chunks = ((g->m + 1) / 2 + 64 * steps - 1) / (64 * steps);
-    RL_LAUNCH((k_lr_project<R>), dim3(chunks, (nrows + RL_LR_ROWS(R) - 1) / RL_LR_ROWS(R)),
-              dim3(64 * RL_LR_WAVES), (size_t)RL_LR_WAVES * R * 65 * sizeof(double), st, X, nrows,
-              g->m, (const double*)g->lr_beta, steps, part != nullptr ? part : g->lr_part);
+    const LrPolicy pol = lr_policy_of(g->kn.lr_policy, measured && R < 36,
+                                      (size_t)nrows * g->m * sizeof(double));
+    lr_project_launch<R>(X, nrows, g->m, (const double*)g->lr_beta, steps,
+                         part != nullptr ? part : g->lr_part, pol, st);
     return chunks;
 }
 template <int R>
@@ -1398,7 +1408,7 @@ static void lr_expand(rl_gridop* g, const double* zhat, int nrows, double* Y, in
     // rule and its measurement are at lr_expand_rpb, rl_lowrank.h
     const int per_cu = 8;
     lr_expand_launch<R>(zhat, nrows, g->m, (const double*)g->lr_beta, Y, accumulate != 0, 16,
-                        per_cu * RL_LR_CUS, g->kn.lr_expand_plain, st);
+                        per_cu * RL_LR_CUS, g->kn.lr_expand_plain, g->kn.lr_policy, st);
 }
 template <int R>
 static void lr_launch(rl_gridop* g, const double* X, double* Y, int nvec, int Q, const double* Cq,
@@ -1411,7 +1421,9 @@ static void lr_launch(rl_gridop* g, const double* X, double* Y, int nvec, int Q,
     // reads-then-writes reach 4.3-4.8.  C5, same box, two alternations: 0.482 / 0.482 ms split
     // against 0.458 / 0.428 as one batch (periodic 0.546 / 0.547 against 0.518 / 0.508): the two
     // queues' workgroups do not share the chip the way one kernel's loads and stores do.)
-    const int chunks = lr_project<R>(g, X, nrows, st);
+    // (the policy's default where it was measured: the projection of a product whose expansion
+    // follows as a launch of its own -- not a solver round's, whose x the previous kernel wrote)
+    const int chunks = lr_project<R>(g, X, nrows, st, nullptr, !accumulate && !deferred);
     lr_mix<R>(g, g->lr_part, chunks, nvec, Q, Cq, Bq, g->lr_zhat, st);
     // (ski_mvm_int: the W kernel expands, k_spmv_w_poly -- ranks 24 and 32 only: at rank 48
     // the evaluation costs more than the two vector passes it saves -- measured, C5

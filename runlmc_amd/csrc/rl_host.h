@@ -95,6 +95,11 @@ struct RlKnobs {
                                  // k_lr_expand_lines: A/B runs, the bit-equality tests), 2 the same with
                                  // its row blocks padded to a multiple of 8 (what k_lr_expand_lines is held against)
                                  // 3 k_lr_expand_lines also where it is not the default (rank >= 36, accumulating)
+    int lr_policy = -1;          // RUNLMC_LR_POLICY: cache policy of k_lr_project's loads and k_lr_expand(_lines)'
+                                 // stores and the projection's depth (rl_lowrank.h LrPolicy): bit 0 nt loads,
+                                 // bits 1-2 stores plain / nt / sc1, bit 3 two rows per wave and a ring of
+                                 // four at rank 24.  0: none of it, whatever the size; unset: the library's
+                                 // choice by instantiation and size (lr_policy_of)
     bool no_precond_approx = false;   // RUNLMC_NO_PRECOND_APPROX: no preconditioner for operators outside the polynomial form
     long long precond_hi_min = 100000;   // RUNLMC_PRECOND_HI_MIN: rows from which an operator without a polynomial row
                                       // gets the 96-function preconditioner

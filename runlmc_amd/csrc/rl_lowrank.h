@@ -34,14 +34,18 @@
 #define RL_LR_RB(R) ((R) <= 24 ? 4 : 2)
 #define RL_LR_G(R) ((R) <= 24 ? 2 : 4)
 #define RL_LR_ROWS(R) (RL_LR_RB(R) * RL_LR_WAVES)   // rows per projection workgroup
-// two projection waves per SIMD (256 registers each); the emulator has no such attribute
+// (both are the DEFAULTS of k_lr_project's template parameters RB and G; the one other depth
+// that is instantiated, rank <= 24 only: 2 rows per wave and a ring of 4 -- LrPolicy below)
+// two projection waves per SIMD (256 registers each) at the default depth, three at the other
+// one (2 x 24 running sums + a ring of 4 x 2 x 2 doubles); the emulator has no such attribute
 // (and no scalar registers: RL_LR_UNIFORM marks a value that is the same in every
 // lane of a wave, so that row pointers and offsets live in SGPRs)
+#define RL_LR_PROJECT_OCC(R, RB) ((RB) == RL_LR_RB(R) ? 2 : 3)
 #if defined(RL_EMU)
-#define RL_LR_PROJECT_ATTR
+#define RL_LR_PROJECT_ATTR(W)
 #define RL_LR_UNIFORM(x) (x)
 #else
-#define RL_LR_PROJECT_ATTR __attribute__((amdgpu_waves_per_eu(2)))
+#define RL_LR_PROJECT_ATTR(W) __attribute__((amdgpu_waves_per_eu(W)))
 #define RL_LR_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
 #endif
 #define RL_LR_TOL 2e-13        // accepted |y_fft - y_lr| / max|y_fft| at set time
@@ -64,6 +68,43 @@ __device__ __forceinline__ int lr_slots(int m) { return (m + 1) / 2; }
 __device__ __forceinline__ double lr_point(int n, int m) {
     return m > 1 ? fma(2.0 / (double)(m - 1), (double)n, -1.0) : 0.0;
 }
+// One element of the expansion's result under store policy SP: plain and `nt` through the
+// element's pointer (the store the kernels always had, with or without the suffix), `sc1` -- which
+// only the buffer instructions' policy argument reaches -- as element `idx` of the row of m doubles at
+// `row` (a wave-uniform base).  The caller's condition stays around it.
+template <int SP>
+__device__ __forceinline__ void lr_put(double* p, double* row, int m, int idx, double v) {
+    if constexpr (SP == RL_POL_PLAIN || SP == RL_POL_NT) rl_ptr_store<SP>(p, v);
+    else rl_row_store<SP>(row, (unsigned)m * 8u, (unsigned)idx * 8u, v);
+}
+
+// Cache policy of the two streaming kernels' accesses and depth of the projection's ring: what
+// RlKnobs::lr_policy (RUNLMC_LR_POLICY) selects.  Bit 0: `nt` loads of x; bits 1-2: stores of
+// y plain / `nt` / `sc1`; bit 3: the projection with 2 rows per wave and a ring of 4 lane-steps
+// (ranks <= 24: the larger ranks have that depth already).  0 is the launch without any of it.
+// Results do not depend on it: hints, and which wave sums which row.
+struct LrPolicy {
+    int load, store;
+    bool deep;
+};
+#define RL_LR_POLICY_MAX 15
+#define RL_LR_STREAM_MIN ((size_t)256 << 20)     // the Infinity Cache: 256 MiB
+// the library's choice (knob < 0) for a product of `bytes` per pass over its vectors: `nt` loads
+// of x, nothing else (profiles/pair_policy: the one combination that won its A/B; see k_lr_project)
+#define RL_LR_POLICY_DEFAULT 1
+static inline LrPolicy lr_policy_of(int knob, bool measured, size_t bytes) {
+    int v = knob;
+    // (a non-plain default only for the instantiations it was measured on, and only when the
+    // stream does not fit the Infinity Cache: below that the consumer of y -- a solver's next
+    // kernel, the sampler -- finds it on chip, and a bypassing store would take that away)
+    if (v < 0) v = measured && bytes > RL_LR_STREAM_MIN ? RL_LR_POLICY_DEFAULT : 0;
+    LrPolicy p;
+    p.load = (v & 1) ? RL_POL_NT : RL_POL_PLAIN;
+    const int s = (v >> 1) & 3;
+    p.store = s == 1 ? RL_POL_NT : (s == 2 ? RL_POL_SC1 : RL_POL_PLAIN);
+    p.deep = ((v >> 3) & 1) != 0;
+    return p;
+}
 
 // ---------------------------------------------------------------------------
 // k_lr_project<R>: part[chunk][row][j] = sum_{n or its mirror in chunk} q_j(n) X[row][n],
@@ -76,12 +117,24 @@ __device__ __forceinline__ double lr_point(int n, int m) {
 // the `steps` points of each lane (a multiple of RL_LR_T, chosen by the host: long
 // chunks amortise the reduction); the 64 lanes are summed once per chunk
 // through LDS.  x values are requested RL_LR_G(R) lane-steps before their use.
-// (Round 3: non-temporal loads for x, A/B in ONE job, three alternations: 0.45 / 0.45 /
-// 0.42 ms per C5 product with plain loads, 0.47 / 0.49 / 0.43 with non-temporal ones -- no
-// gain, and the run-to-run spread on one box is as large as the box-to-box one.)
-// (Round 3, same protocol: two rows per wave and a ring of four lane-steps at rank 24 --
-// 148 registers, three waves per SIMD, half as much again in flight per CU: 0.497 / 0.498 /
-// 0.498 ms against 0.494 / 0.492 / 0.492.  Neither occupancy nor bytes in flight bound it.)
+// LP is the cache policy of the loads of x, RB and G the depth (LrPolicy above).  Measured on
+// the PAIR -- projection and expansion alternating in steady state on separate 1.03 GB buffers,
+// the ring pipelined (tools/lr_pattern_probe.hip `pair`, profiles/pair_policy/pair.txt; C5
+// shape, rank 24, m = 100 004, medians of 11, two passes), not on the kernel alone:
+//   plain loads            projection 255 us   expansion behind it 188   pair 443-445
+//   nt loads               projection 188      expansion 221-226         pair 411-414
+//   nt loads, 2 x 4        projection 180      expansion 222-226         pair 402-406
+//   2 x 4, plain loads     projection 253      expansion 188             pair 441-442
+// A plain load has to evict one of the previous expansion's dirty lines to make room, an nt
+// load does not: the projection reads at its back-to-back rate again, and the drain it no
+// longer waits for costs the NEXT expansion about half of what was saved.  bench.py A/B, five
+// alternations in one job (ab_rbf_2.jsonl): 0.4585 -> 0.4315 ms per C5 product, faster in every
+// alternation, ranges 0.003 / 0.006: nt loads are the default where that was measured (rank
+// < 36, not accumulating, more than 256 MiB per pass: lr_policy_of).  The other depth -- 154
+// registers, three waves per SIMD, 16 loads in flight per wave as before -- gains 8 us in the
+// probe and nothing in the A/B (ab_rbf.jsonl, slower than nt alone in every alternation): an
+// instance behind the knob only.  Rank 36 (periodic) does not gain from nt loads
+// (ab_periodic.jsonl: 0.5486 -> 0.5553, inside the spread) and keeps plain ones.
 // (Round 5: three rows per wave and a ring of two at rank 36 -- 256 registers, 8 spilled:
 // 336 against 300-315 us per C5 projection.)
 // (Measured and dropped, round 3: the projection as a tall-skinny product on the fp64
@@ -92,11 +145,11 @@ __device__ __forceinline__ double lr_point(int n, int m) {
 // against 0.19 ms per C5 projection.  Feeding it needs the LDS transposition of
 // rl_filter.h's tiles, which costs what the matrix cores save here.)
 // ---------------------------------------------------------------------------
-template <int R>
-__global__ void __launch_bounds__(64 * RL_LR_WAVES) RL_LR_PROJECT_ATTR
+template <int R, int LP = RL_POL_PLAIN, int RB = RL_LR_RB(R), int G = RL_LR_G(R)>
+__global__ void __launch_bounds__(64 * RL_LR_WAVES) RL_LR_PROJECT_ATTR(RL_LR_PROJECT_OCC(R, RB))
 k_lr_project(const double* __restrict__ X, int nrows, int m, const double* __restrict__ beta,
              int steps, double* __restrict__ part) {
-    constexpr int RB = RL_LR_RB(R), G = RL_LR_G(R), ROWS = RL_LR_ROWS(R);
+    constexpr int ROWS = RB * RL_LR_WAVES;
     RL_SMEM(smem);
     double* red = reinterpret_cast<double*>(smem);       // [WAVES][R][65]
     const int tid = threadIdx.x, lane = tid & 63, wave = RL_LR_UNIFORM(tid >> 6);
@@ -134,11 +187,11 @@ k_lr_project(const double* __restrict__ X, int nrows, int m, const double* __res
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
             if constexpr (RING) {
-                xr[slot][r] = rl_row_load(xrow[r], rowbytes, (unsigned)nc * 8u);
-                xm[slot][r] = rl_row_load(xrow[r], rowbytes, (unsigned)(m - 1 - nc) * 8u);
+                xr[slot][r] = rl_row_load<LP>(xrow[r], rowbytes, (unsigned)nc * 8u);
+                xm[slot][r] = rl_row_load<LP>(xrow[r], rowbytes, (unsigned)(m - 1 - nc) * 8u);
             } else {
-                xr[slot][r] = xrow[r][nc];
-                xm[slot][r] = xrow[r][m - 1 - nc];
+                xr[slot][r] = rl_ptr_load<LP>(xrow[r] + nc);
+                xm[slot][r] = rl_ptr_load<LP>(xrow[r] + (m - 1 - nc));
             }
         }
     };
@@ -219,6 +272,37 @@ k_lr_project(const double* __restrict__ X, int nrows, int m, const double* __res
         }
         __syncthreads();
     }
+}
+
+// Host side: ONE launcher of the projection for every call site (as lr_expand_launch below for
+// the expansion).  `steps` comes from the caller and does not depend on the policy: chunk
+// length, a lane's order of summation and the LDS reduction are the same for every instance.
+template <int R, int LP, int RB, int G>
+static void lr_project_launch_as(const double* X, int nrows, int m, const double* beta, int steps,
+                                 double* part, hipStream_t st) {
+    const int chunks = ((m + 1) / 2 + 64 * steps - 1) / (64 * steps);
+    constexpr int ROWS = RB * RL_LR_WAVES;
+    RL_LAUNCH((k_lr_project<R, LP, RB, G>), dim3(chunks, (nrows + ROWS - 1) / ROWS),
+              dim3(64 * RL_LR_WAVES), (size_t)RL_LR_WAVES * R * 65 * sizeof(double), st, X, nrows, m,
+              beta, steps, part);
+}
+template <int R>
+static void lr_project_launch(const double* X, int nrows, int m, const double* beta, int steps,
+                              double* part, LrPolicy pol, hipStream_t st) {
+    constexpr int RB = RL_LR_RB(R), G = RL_LR_G(R);
+    if constexpr (R <= 24) {
+        if (pol.deep) {
+            if (pol.load == RL_POL_NT)
+                lr_project_launch_as<R, RL_POL_NT, 2, 4>(X, nrows, m, beta, steps, part, st);
+            else
+                lr_project_launch_as<R, RL_POL_PLAIN, 2, 4>(X, nrows, m, beta, steps, part, st);
+            return;
+        }
+    }
+    if (pol.load == RL_POL_NT)
+        lr_project_launch_as<R, RL_POL_NT, RB, G>(X, nrows, m, beta, steps, part, st);
+    else
+        lr_project_launch_as<R, RL_POL_PLAIN, RB, G>(X, nrows, m, beta, steps, part, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -332,7 +416,13 @@ k_lr_mix(const double* __restrict__ part, int nchunks, int nvec, int D, int r, i
 // and the odd degrees are summed separately, y(n) is their sum and y(mirror)
 // their difference.  (Measured and dropped: two slots per thread 318 vs 250 us
 // at C5, two rows of coefficients in flight 324 -- the scalar registers run
-// out --, non-temporal stores 271 vs 243.  Round 3: the expansion of the larger
+// out.  SP, the cache policy of the stores of y, measured on the pair as LP of k_lr_project
+// above, rank 24, m = 100 004: nt stores leave the next projection at 186-189 us (plain: 255)
+// and cost the expansion 282 against 188 -- pair 468-472 against 443-445; sc1 stores 278 and a
+// projection of 270-273 -- pair 548-552.  At m = 100 000 (k_lr_expand, rows on lines) nt
+// stores 200 against 172-175, sc1 170; with nt loads on top neither is told apart from nt
+// loads alone (367-377).  Stores keep the plain policy; both others sit behind the knob.
+// Round 3: the expansion of the larger
 // ranks on the fp64 matrix cores -- Zhat fragments in registers, the chunk's basis in
 // LDS, 16 rows x 16 slots per tile, 128-byte stores: 555 vs 330-370 us at rank 48.)
 // This kernel runs when rows start on 128-byte lines (16 divides m, Y line-aligned) and under
@@ -344,7 +434,7 @@ k_lr_mix(const double* __restrict__ part, int nchunks, int nvec, int D, int r, i
 // of a row -- one store in flight per wave, which is what bounded the kernel.  The plain
 // kernel has no load at all, the accumulating one loads unconditionally from the clamped
 // positions.)
-template <int R, bool ACC>
+template <int R, bool ACC, int SP = RL_POL_PLAIN>
 __global__ void __launch_bounds__(256)
 k_lr_expand(const double* __restrict__ Zhat, int nrows, int m, const double* __restrict__ beta,
             int rows_per_block, double* __restrict__ Y) {
@@ -399,8 +489,8 @@ k_lr_expand(const double* __restrict__ Zhat, int nrows, int m, const double* __r
             o0 = *y0;
             o1 = *y1;
         }
-        if (live) *y0 = (ev + od) + o0;
-        if (pair) *y1 = (ev - od) + o1;
+        if (live) lr_put<SP>(y0, Y + (size_t)row * m, m, nc, (ev + od) + o0);
+        if (pair) lr_put<SP>(y1, Y + (size_t)row * m, m, mir, (ev - od) + o1);
     }
 }
 
@@ -429,7 +519,7 @@ k_lr_expand(const double* __restrict__ Zhat, int nrows, int m, const double* __r
 // LDS so that it leaves in whole lines too -- one barrier per row; 187-190 us at C5 against
 // 185-186 without it.  tools/lr_pattern_probe.hip holds that variant.)
 // ---------------------------------------------------------------------------
-template <int R, bool ACC>
+template <int R, bool ACC, int SP = RL_POL_PLAIN>
 __global__ void __launch_bounds__(256)
 k_lr_expand_lines(const double* __restrict__ Zhat, int nrows, int m, const double* __restrict__ beta,
                   int rows_per_block, int period, int nby, double* __restrict__ Y) {
@@ -481,8 +571,8 @@ k_lr_expand_lines(const double* __restrict__ Zhat, int nrows, int m, const doubl
             o0 = *y0;
             o1 = *y1;
         }
-        if (live) *y0 = (ev + od) + o0;
-        if (pair) *y1 = (ev - od) + o1;
+        if (live) lr_put<SP>(y0, Y + (size_t)row * m, m, nc, (ev + od) + o0);
+        if (pair) lr_put<SP>(y1, Y + (size_t)row * m, m, mir, (ev - od) + o1);
     }
 }
 
@@ -519,10 +609,27 @@ static inline LrLinesGrid lr_expand_lines_grid(int nrows, int m, int rpb_max, in
 // m and Y starts on a line: nothing to gain -- or the instantiation keeps k_lr_expand (below), 1
 // k_lr_expand, 2 k_lr_expand with gridDim.y padded, 3 k_lr_expand_lines for those
 // instantiations too (their tests and A/B runs).  `pad8` is false in the pattern probe only.
+// `policy` (RlKnobs::lr_policy; < 0: the library's choice by instantiation and size, lr_policy_of).
+template <int R, int SP>
+static void lr_expand_launch_as(const double* zhat, int nrows, int m, const double* beta, double* Y,
+                                bool accumulate, int rpb_max, int round_wgs, int plain,
+                                hipStream_t st, bool pad8);
 template <int R>
 static void lr_expand_launch(const double* zhat, int nrows, int m, const double* beta, double* Y,
-                             bool accumulate, int rpb_max, int round_wgs, int plain,
+                             bool accumulate, int rpb_max, int round_wgs, int plain, int policy,
                              hipStream_t st, bool pad8 = true) {
+    const LrPolicy pol = lr_policy_of(policy, R < 36 && !accumulate, (size_t)nrows * m * sizeof(double));
+    if (pol.store == RL_POL_NT)
+        lr_expand_launch_as<R, RL_POL_NT>(zhat, nrows, m, beta, Y, accumulate, rpb_max, round_wgs, plain, st, pad8);
+    else if (pol.store == RL_POL_SC1)
+        lr_expand_launch_as<R, RL_POL_SC1>(zhat, nrows, m, beta, Y, accumulate, rpb_max, round_wgs, plain, st, pad8);
+    else
+        lr_expand_launch_as<R, RL_POL_PLAIN>(zhat, nrows, m, beta, Y, accumulate, rpb_max, round_wgs, plain, st, pad8);
+}
+template <int R, int SP>
+static void lr_expand_launch_as(const double* zhat, int nrows, int m, const double* beta, double* Y,
+                                bool accumulate, int rpb_max, int round_wgs, int plain,
+                                hipStream_t st, bool pad8) {
     const int p0 = (int)((reinterpret_cast<unsigned long long>(Y) >> 3) & 15ull);
     // (k_lr_expand_lines is the default for ranks below 36, not accumulating: the headline's
     // instantiations.  The others were faster with it too -- profiles/expand_lines, value 3 --
@@ -534,18 +641,18 @@ static void lr_expand_launch(const double* zhat, int nrows, int m, const double*
         const int nby = (nrows + rpb - 1) / rpb;
         const dim3 grid(nbx, plain == 2 ? (nby + 7) / 8 * 8 : nby);
         if (accumulate)
-            RL_LAUNCH((k_lr_expand<R, true>), grid, dim3(256), 0, st, zhat, nrows, m, beta, rpb, Y);
+            RL_LAUNCH((k_lr_expand<R, true, SP>), grid, dim3(256), 0, st, zhat, nrows, m, beta, rpb, Y);
         else
-            RL_LAUNCH((k_lr_expand<R, false>), grid, dim3(256), 0, st, zhat, nrows, m, beta, rpb, Y);
+            RL_LAUNCH((k_lr_expand<R, false, SP>), grid, dim3(256), 0, st, zhat, nrows, m, beta, rpb, Y);
         return;
     }
     const LrLinesGrid g = lr_expand_lines_grid(nrows, m, rpb_max, round_wgs);
     const dim3 grid(g.nbx, pad8 ? (g.nby + 7) / 8 * 8 : g.nby);
     if (accumulate)
-        RL_LAUNCH((k_lr_expand_lines<R, true>), grid, dim3(256), 0, st, zhat, nrows, m, beta, g.rpb,
+        RL_LAUNCH((k_lr_expand_lines<R, true, SP>), grid, dim3(256), 0, st, zhat, nrows, m, beta, g.rpb,
                   g.period, g.nby, Y);
     else
-        RL_LAUNCH((k_lr_expand_lines<R, false>), grid, dim3(256), 0, st, zhat, nrows, m, beta, g.rpb,
+        RL_LAUNCH((k_lr_expand_lines<R, false, SP>), grid, dim3(256), 0, st, zhat, nrows, m, beta, g.rpb,
                   g.period, g.nby, Y);
 }
 

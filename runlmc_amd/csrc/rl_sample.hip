@@ -385,8 +385,10 @@ extern "C" int rl_sampler_spectrum_host(const rl_sampler* h, int q, double* out)
 template <int R>
 static void smp_expand(rl_sampler* h, double* U, int nrows, bool accumulate, hipStream_t st) {
     // (one round of four workgroups per compute unit, whatever the number of rows)
+    // (a store policy from the knob only: the library's choice was measured on the product)
+    const int policy = h->g->kn.lr_policy < 0 ? 0 : h->g->kn.lr_policy;
     lr_expand_launch<R>((const double*)h->zhat, nrows, h->m, (const double*)h->g->lr_beta, U, accumulate,
-                        0, 4 * RL_LR_CUS, h->g->kn.lr_expand_plain, st);
+                        0, 4 * RL_LR_CUS, h->g->kn.lr_expand_plain, policy, st);
 }
 
 extern "C" int rl_sampler_draw(rl_sampler* h, const double* Z, double* U, int nsamp, void* stream) {

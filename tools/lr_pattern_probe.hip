@@ -10,6 +10,8 @@
 // the row blocks padded to a multiple of 8 (column neighbours on one XCD); and, to tell the rungs apart, rung 4
 // = rung 0 + that padding alone (k_lr_expand has nothing to do in a surplus row block), rung 5 = rung 1 + the
 // padding (no LDS: the library's default).  -DPROBE_RUNGS=<bit mask> compiles a subset (default 0x3F: all six).
+// Part 5 (`lr_pattern_probe pair`: that part alone), profiles/pair_policy: the two kernels alternating on
+// SEPARATE buffers under every cache policy of the loads and the stores and both depths of the projection.
 #include "rl_kernels.h"
 #include "rl_lowrank.h"
 #include <cstdio>
@@ -281,14 +283,14 @@ static void expand_rung(const double* zhat, int nrows, int m, const double* beta
     if constexpr (RUNG == 2 || RUNG == 3) {
         const int p0 = (int)((reinterpret_cast<unsigned long long>(Y) >> 3) & 15ull);
         if ((m & 15) == 0 && p0 == 0) {
-            lr_expand_launch<R>(zhat, nrows, m, beta, Y, false, 16, 8 * RL_LR_CUS, 1, 0);
+            lr_expand_launch<R>(zhat, nrows, m, beta, Y, false, 16, 8 * RL_LR_CUS, 1, 0, 0);
             return;
         }
         const LrLinesGrid g = lr_expand_lines_grid(nrows, m, 16, 8 * RL_LR_CUS);
         hipLaunchKernelGGL((k_probe_expand_staged<R>), dim3(g.nbx, RUNG == 3 ? (g.nby + 7) / 8 * 8 : g.nby), dim3(256), 0,
                            0, zhat, nrows, m, beta, g.rpb, g.period, g.nby, Y);
     } else {
-        lr_expand_launch<R>(zhat, nrows, m, beta, Y, false, 16, 8 * RL_LR_CUS, RUNG == 0 ? 1 : (RUNG == 4 ? 2 : 0), 0,
+        lr_expand_launch<R>(zhat, nrows, m, beta, Y, false, 16, 8 * RL_LR_CUS, RUNG == 0 ? 1 : (RUNG == 4 ? 2 : 0), 0, 0,
                             RUNG == 5);
     }
 }
@@ -357,7 +359,90 @@ static void ladder(int m, int nrows) {
     ladder_rung<R, 5>(m, nrows, 32);
 }
 
+// ---- part 5 (`lr_pattern_probe pair`: that part alone), profiles/pair_policy: projection and expansion
+// ALTERNATING in steady state on SEPARATE buffers X and Y of 1.03 GB each, as a product does (part 1 alternates
+// on one buffer), under every value of RUNLMC_LR_POLICY (rl_lowrank.h LrPolicy: load policy x store policy x
+// depth of the projection), through the library's two launchers.  No host synchronisation inside the 13 pairs
+// of a combination (two to warm up): each kernel starts behind the other one's traffic.  What a policy buys
+// shows in the kernel BEHIND the access it changes, so each kernel and the pair's sum are reported.
+struct PairBufs {
+    double *X, *Y, *part, *beta, *zhat;
+};
+template <int R>
+static void pair_combo(const PairBufs& b, int m, int nrows, int steps, int policy) {
+    constexpr int REPS = 13, WARM = 2;
+    static hipEvent_t ev[3 * REPS];
+    static bool have = false;
+    if (!have) {
+        for (hipEvent_t& e : ev) hipEventCreate(&e);
+        have = true;
+    }
+    const LrPolicy pol = lr_policy_of(policy, true, (size_t)nrows * m * 8);
+    for (int rep = 0; rep < REPS; ++rep) {
+        hipEventRecord(ev[3 * rep]);
+        lr_project_launch<R>(b.X, nrows, m, b.beta, steps, b.part, pol, 0);
+        hipEventRecord(ev[3 * rep + 1]);
+        lr_expand_launch<R>(b.zhat, nrows, m, b.beta, b.Y, false, 16, 8 * RL_LR_CUS, 0, policy, 0);
+        hipEventRecord(ev[3 * rep + 2]);
+    }
+    hipEventSynchronize(ev[3 * REPS - 1]);
+    std::vector<float> tp, te, ts;
+    for (int rep = WARM; rep < REPS; ++rep) {
+        float p, e;
+        hipEventElapsedTime(&p, ev[3 * rep], ev[3 * rep + 1]);
+        hipEventElapsedTime(&e, ev[3 * rep + 1], ev[3 * rep + 2]);
+        tp.push_back(p);
+        te.push_back(e);
+        ts.push_back(p + e);
+    }
+    std::sort(tp.begin(), tp.end());
+    std::sort(te.begin(), te.end());
+    std::sort(ts.begin(), ts.end());
+    const size_t h = tp.size() / 2;
+    printf("pair rank %2d m %6d policy %2d (load %-5s store %-5s rows x ring %s): project %6.1f (%6.1f %6.1f) | expand %6.1f "
+           "(%6.1f %6.1f) | sum %6.1f (%6.1f %6.1f) us\n",
+           R, m, policy, pol.load == RL_POL_NT ? "nt" : "plain",
+           pol.store == RL_POL_NT ? "nt" : (pol.store == RL_POL_SC1 ? "sc1" : "plain"), pol.deep ? "2x4" : "4x2",
+           1e3 * tp[h], 1e3 * tp.front(), 1e3 * tp.back(), 1e3 * te[h], 1e3 * te.front(), 1e3 * te.back(), 1e3 * ts[h],
+           1e3 * ts.front(), 1e3 * ts.back());
+    fflush(stdout);
+}
+template <int R>
+static void pair_all(const PairBufs& b, int m, int nrows) {
+    // (the launch without any policy first and last: what moves between the two is drift)
+    for (int policy : {0, 1, 2, 3, 4, 5, 8, 9, 10, 11, 12, 13, 0}) pair_combo<R>(b, m, nrows, 32, policy);
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "pair") {
+        const int nrows = 1290, mmax = 100004;
+        PairBufs b;
+        const size_t bytes = (size_t)nrows * mmax * 8;
+        const int chunks = ((mmax + 1) / 2 + 64 * 32 - 1) / (64 * 32);
+        if (hipMalloc(&b.X, bytes) != hipSuccess || hipMalloc(&b.Y, bytes) != hipSuccess ||
+            hipMalloc(&b.part, (size_t)chunks * nrows * 24 * 8) != hipSuccess || hipMalloc(&b.beta, 64 * 8) != hipSuccess ||
+            hipMalloc(&b.zhat, (size_t)nrows * 24 * 8) != hipSuccess) {
+            fprintf(stderr, "pair: allocation failed\n");
+            return 1;
+        }
+        hipMemset(b.X, 0, bytes);
+        hipMemset(b.Y, 0, bytes);
+        hipMemset(b.beta, 0, 64 * 8);
+        hipMemset(b.zhat, 0, (size_t)nrows * 24 * 8);
+        printf("median (min max) of 11, us; sum = the pair's two kernels, per repetition\n");
+        for (int pass = 0; pass < 2; ++pass) {
+            printf("-- pass %d\n", pass);
+            for (int m : {100004, 100000}) {
+                pair_all<2>(b, m, nrows);
+                pair_all<24>(b, m, nrows);
+            }
+        }
+        if (hipDeviceSynchronize() != hipSuccess) {
+            fprintf(stderr, "pair: %s\n", hipGetErrorString(hipGetLastError()));
+            return 1;
+        }
+        return 0;
+    }
     if (argc > 1 && std::string(argv[1]) == "lines") {
         // (two passes: what moves between them is this box's spread, not a rung)
         for (int pass = 0; pass < 2; ++pass) {
