@@ -418,6 +418,25 @@ int rl_exact_set_factors(rl_exact* h, const double* X, const int* lens, int D, i
                          const int* nfact, const int* leaf_kinds, const double* leaf_params,
                          const int* scaled, const double* scales, const int* active_cols,
                          const double* B, const double* noise);
+/* The same with every LEAF on a distance of its own: a latent kernel is the separable product
+ *   c prod_{f < nfact[q]} k_f(r_f),  r_f the Euclidean distance over leaf f's own input columns
+ * (runlmc_amd/kern/stationary.py: Separable, RBF.ard; the reference has neither):
+ *   nfact, leaf_kinds, leaf_params, scaled, scales, X, lens, B, noise as rl_exact_set_factors;
+ *   leaf_cols host [Q][3][4]: the column indices of leaf f of kernel q, -1 after the last; the
+ *   lists of factors f >= nfact[q] are not read.  Leaves of one kernel may share columns (a Product
+ *   factor of a Separable) -- nothing here asks the lists to be disjoint.
+ * Derivative order and slots: identical to rl_exact_set_factors.  Limits: at most 3 leaves and
+ * 4 columns per leaf; Q + sum_q p_q <= 32 (RL_ELIMIT, the message names the count).  RL_EINVAL: a
+ * column index >= P, a leaf without a column, nfact outside 1 .. 3, an unknown leaf kind.
+ * Every leaf's distance is summed as a kernel's is, so a set whose leaves all list their kernel's
+ * columns computes what rl_exact_set_factors computes, bit for bit.  Every later call works
+ * unchanged in the state this leaves; a later rl_exact_set / rl_exact_set_factors on the same
+ * handle returns to those paths.  (Joined ABI version 8 without a bump: no declared signature
+ * changed.)                                                                                    */
+int rl_exact_set_separable(rl_exact* h, const double* X, const int* lens, int D, int Q,
+                           const int* nfact, const int* leaf_kinds, const double* leaf_params,
+                           const int* leaf_cols, const int* scaled, const double* scales,
+                           const double* B, const double* noise);
 /* K into the device buffer (lower triangle; rl_exact_factor does it when needed). */
 int rl_exact_assemble(rl_exact* h);
 /* Blocked Cholesky K = L L^T in place (cho_factor, likelihood.py:153) and

@@ -70,6 +70,7 @@ _SIGNATURES = {
     'rl_exact_destroy': [_vp],
     'rl_exact_set': [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
     'rl_exact_set_factors': [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'rl_exact_set_separable': [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'rl_exact_assemble': [_vp],
     'rl_exact_factor': [_vp, _c_dbl_p, _c_int_p],
     'rl_exact_solve': [_vp, _vp, _vp, _i, _vp],

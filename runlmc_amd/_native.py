@@ -665,6 +665,62 @@ def exact_factor_descriptors(kernels):
     return nfact, leaves, params, scaled, scales, np.array(cols, dtype=np.int32), nder
 
 
+def exact_is_separable(kernels):
+    """Whether a kernel set needs rl_exact_set_separable: a Separable anywhere in it."""
+    from .kern.stationary import Scaled, Separable
+    return any(type(k.k if type(k) is Scaled else k) is Separable for k in kernels)
+
+
+def exact_separable_descriptors(kernels):
+    """(factors per kernel [Q], leaf kinds [Q, 3], leaf parameters [Q, 3, 2], leaf columns
+    [Q, 3, 4], scale flags [Q], scales [Q], parameters per kernel) for rl_exact_set_separable:
+    every kernel a (Scaled) leaf, Product of leaves or Separable; the leaves of a kernel on one
+    distance all list that kernel's columns.  Derivatives per kernel as exact_factor_descriptors'.
+    A kernel the device cannot take raises NotImplementedError naming it."""
+    from .kern.stationary import Cosine, Product, Scaled, Separable, StdPeriodic
+    codes = _exact_leaf_codes()
+    Q = len(kernels)
+    nfact = np.zeros(Q, dtype=np.int32)
+    leaves = np.zeros((Q, EXACT_MAX_FACT), dtype=np.int32)
+    params = np.zeros((Q, EXACT_MAX_FACT, 2), dtype=np.float64)
+    lcols = np.full((Q, EXACT_MAX_FACT, EXACT_MAX_COLS), -1, dtype=np.int32)
+    scaled = np.zeros(Q, dtype=np.int32)
+    scales = np.zeros(Q, dtype=np.float64)
+    nder = []
+    for q, k in enumerate(kernels):
+        inner = k.k if type(k) is Scaled else k
+        if type(inner) is Separable:
+            pairs = inner.leaves()
+        else:
+            pairs = [(leaf, k.active_dims) for leaf in
+                     (inner.factors if type(inner) is Product else [inner])]
+        if len(pairs) > EXACT_MAX_FACT:
+            raise NotImplementedError('the exact likelihood takes products of at most %d leaves, '
+                                      '%s has %d' % (EXACT_MAX_FACT, k.name, len(pairs)))
+        for f, (leaf, dims) in enumerate(pairs):
+            if type(leaf) not in codes:
+                raise NotImplementedError(
+                    'the exact likelihood has no device kernel for %s (in %s)'
+                    % (type(leaf).__name__, k.name))
+            dims = list(dims if dims is not None else ())
+            if not dims:
+                raise ValueError('kernel %s has no active dimensions' % k.name)
+            if len(dims) > EXACT_MAX_COLS:
+                raise NotImplementedError('the exact likelihood takes leaves on at most %d input '
+                                          'dimensions, %s of %s has %d'
+                                          % (EXACT_MAX_COLS, leaf.name, k.name, len(dims)))
+            leaves[q, f] = codes[type(leaf)]
+            params[q, f, 0] = leaf.frequency if type(leaf) is Cosine else leaf.inv_lengthscale
+            if type(leaf) is StdPeriodic:
+                params[q, f, 1] = leaf.period
+            lcols[q, f, :len(dims)] = dims
+        nfact[q] = len(pairs)
+        if type(k) is Scaled:
+            scaled[q], scales[q] = 1, k.scale
+        nder.append(sum(2 if type(leaf) is StdPeriodic else 1 for leaf, _ in pairs) + int(scaled[q]))
+    return nfact, leaves, params, lcols, scaled, scales, nder
+
+
 class ExactOp:
     """Device handle of the dense exact LMC covariance, its Cholesky factor and K^-1
     (include/runlmc_hip.h: rl_exact_*)."""
@@ -700,9 +756,14 @@ class ExactOp:
     def set(self, X, lens, kernels, coreg_mats, noise):
         """Data X (n, P) with rows the outputs concatenated, `lens` per output, the kernels
         (runlmc_amd.kern), B_q (Q, D, D) and the noise (D,) -- rl_exact_set, or
-        rl_exact_set_factors when the set holds a Product or a Cosine."""
-        composite = exact_is_composite(kernels)
-        if composite:
+        rl_exact_set_factors when the set holds a Product or a Cosine, or rl_exact_set_separable
+        when it holds a Separable."""
+        separable = exact_is_separable(kernels)
+        composite = not separable and exact_is_composite(kernels)
+        if separable:
+            nfact, leaves, lparams, lcols, scaled, scales, nder = exact_separable_descriptors(kernels)
+            kinds = nfact
+        elif composite:
             nfact, leaves, lparams, scaled, scales, cols, nder = exact_factor_descriptors(kernels)
             kinds = nfact
         else:
@@ -719,7 +780,11 @@ class ExactOp:
         X, lens = self._rows(X, lens, 'rl_exact_set')
         if X.shape[0] != self.n:
             raise ValueError('the handle holds %d points, got %d' % (self.n, X.shape[0]))
-        if composite:
+        if separable:
+            self.lib.call('rl_exact_set_separable', self._h, host_ptr(X), host_ptr(lens), D, len(kinds),
+                          host_ptr(nfact), host_ptr(leaves), host_ptr(lparams), host_ptr(lcols),
+                          host_ptr(scaled), host_ptr(scales), host_ptr(B), host_ptr(noise))
+        elif composite:
             self.lib.call('rl_exact_set_factors', self._h, host_ptr(X), host_ptr(lens), D, len(kinds),
                           host_ptr(nfact), host_ptr(leaves), host_ptr(lparams), host_ptr(scaled),
                           host_ptr(scales), host_ptr(cols), host_ptr(B), host_ptr(noise))

@@ -23,6 +23,7 @@ import torch
 from .iterative import Iterative
 from .._native import Sampler, normal_fill, pathwise_residual, sampler_length
 from .._lib import as_f64
+from ..kern.stationary import Lags, kernel_values
 
 _LOG = logging.getLogger(__name__)
 
@@ -69,7 +70,7 @@ class GridSampler:
     """Prior draws u ~ N(0, sum_q B_q (x) T_q) of one grid term on the device.
 
     grid_kernel: the term's GridKernel (or its GridOp), holding the CURRENT parameters;
-    kernels[q].from_dist gives top row q at any distance; coreg_vecs[q] (R_q, D) or None,
+    kernels[q].from_dist (from_lags for a Separable) gives top row q at any distance; coreg_vecs[q] (R_q, D) or None,
     coreg_diags[q] (D,); axes: the grid's axes (one or two regular arrays).
     forms: None -- rows the operator runs in its polynomial form take it, the others embed;
     'embedding' -- every row embeds.  max_embed: the embedding is at most that multiple of the
@@ -123,7 +124,9 @@ class GridSampler:
                 lags = np.meshgrid(*[h * np.arange(n // 2 + 1) for h, n in zip(steps, lengths)],
                                    indexing='ij')
                 dist = np.sqrt(sum(np.square(g) for g in lags))
-                ext = [as_f64(kernels[q].from_dist(dist)) for q in emb]
+                # (a Separable row is evaluated at the mesh's per-axis lags, axis order = the grid's)
+                at = Lags(lags, dist)
+                ext = [as_f64(kernel_values(kernels[q], at)) for q in emb]
             return lengths, self._h.set(channels, row_forms, lengths, ext, rank, sq)
 
         embed = 2

@@ -9,7 +9,8 @@
 //   - kernel descriptors: at most EX_MAX_SLOT = 32 values of k_q and dk_q / dtheta_p in all
 //     (Q + sum_q p_q), EX_MAX_COLS = 4 active input columns per kernel, D <= EX_MAX_D = 64;
 //   - a latent kernel is c prod_f k_f(r) of 1 .. EX_MAX_FACT = 3 leaf kernels on one distance
-//     (ex_desc / ex_eval_fact below): at most 2 * 3 + 1 = 7 derivatives per kernel.
+//     (ex_desc / ex_eval_fact below): at most 2 * 3 + 1 = 7 derivatives per kernel; a separable
+//     set gives every leaf a distance over its own <= EX_MAX_COLS columns (ex_eval_sep).
 //
 // k_ex_gemm is the one update every blocked step uses (trailing SYRK of the factorisation,
 // off-diagonal blocks of the triangular solves, L^-1 and L^-T L^-1): C (+)= s A B^T on 64 x 64
@@ -151,8 +152,11 @@ __device__ __host__ __forceinline__ int ex_desc_nder(int desc) {
 // factor counts as the exact constant 1, so a single factor keeps ex_eval's bits, the scale is
 // applied as ex_eval applies it, and a NaN leaf value (StdPeriodic's convention) stays NaN.
 // ---------------------------------------------------------------------------
-template <int NF>
-__device__ __forceinline__ void ex_eval_fact(int desc, const double* prm, int q, double r, double v[8]) {
+// SEP (separable sets, see ex_eval_sep): leaf 0 at r, leaves 1 and 2 at r1 and r2 -- a distance
+// per leaf; otherwise every leaf at r and r1, r2 are not read.
+template <int NF, bool SEP = false>
+__device__ __forceinline__ void ex_eval_fact(int desc, const double* prm, int q, double r, double v[8],
+                                             double r1 = 0.0, double r2 = 0.0) {
     const double* p0 = prm + 4 * q;
     const double* p1 = prm + EX_PRM2 + 4 * q;
     const int nf = ex_desc_nf(desc);
@@ -165,7 +169,7 @@ __device__ __forceinline__ void ex_eval_fact(int desc, const double* prm, int q,
         if (f < nf) {
             const int leaf = ex_desc_leaf(desc, f);
             double t[4];
-            ex_leaf(leaf, f == 0 ? p0 : p1 + 2 * (f - 1), r, t);
+            ex_leaf(leaf, f == 0 ? p0 : p1 + 2 * (f - 1), SEP ? (f == 0 ? r : f == 1 ? r1 : r2) : r, t);
             k[f] = t[0];
             d[f][0] = t[1];
             if (leaf == EX_STDPERIODIC) d[f][1] = t[2];
@@ -215,13 +219,34 @@ __device__ __forceinline__ double ex_dist(const double* xa, const double* xb, co
 }
 
 // ---------------------------------------------------------------------------
+// Separable sets (rl_exact_set_separable): a latent kernel is c prod_f k_f(r_f), every leaf on the
+// distance over ITS OWN columns.  The kernels below take SEP = true and, in place of the column
+// table of the kernels [Q][EX_MAX_COLS], the table of the leaves [Q][EX_MAX_FACT][EX_MAX_COLS]
+// (-1 after a leaf's last column).  Each leaf's distance is ex_dist itself, so leaves that share
+// their kernel's columns get the bits of the one-distance path.
+// ---------------------------------------------------------------------------
+#define EX_LEAF_COLS (EX_MAX_FACT * EX_MAX_COLS)
+
+// value and derivatives (ex_eval_fact's fixed places) of separable kernel q between xa and xb;
+// lq: the kernel's EX_MAX_FACT column lists
+__device__ __forceinline__ void ex_eval_sep(int desc, const double* prm, int q, const double* xa,
+                                            const double* xb, const int* lq, double v[8]) {
+    const int nf = ex_desc_nf(desc);
+    const double r0 = ex_dist(xa, xb, lq);
+    const double r1 = nf > 1 ? ex_dist(xa, xb, lq + EX_MAX_COLS) : 0.0;
+    const double r2 = nf > 2 ? ex_dist(xa, xb, lq + 2 * EX_MAX_COLS) : 0.0;
+    ex_eval_fact<EX_MAX_FACT, true>(desc, prm, q, r0, v, r1, r2);
+}
+
+// ---------------------------------------------------------------------------
 // out[i][j] = sum_q B_q[oa(i), ob(j)] k_q(r_q(xa_i, xb_j))  (+ noise[oa(i)] where i + diag_off == j)
 // for i < nrows, j < ncols; lower != 0 skips tiles above the diagonal.  grid (ceil(ncols / 64),
 // ceil(nrows / 64)), block 256: a thread fills 16 entries of a 64 x 64 tile, rows of 64
 // consecutive columns per quarter of the block.  NF: the most factors of any kernel of the
-// handle (1: plain kernels, ex_eval as it stands; EX_MAX_FACT otherwise).
+// handle (1: plain kernels, ex_eval as it stands; EX_MAX_FACT otherwise).  SEP: see ex_eval_sep
+// (NF = EX_MAX_FACT, cols the table of the leaves).
 // ---------------------------------------------------------------------------
-template <int NF>
+template <int NF, bool SEP = false>
 __global__ void __launch_bounds__(256)
 k_ex_assemble(double* __restrict__ out, long long ldo, int nrows, int ncols,
               const double* __restrict__ Xa, const int* __restrict__ oa,
@@ -238,6 +263,13 @@ k_ex_assemble(double* __restrict__ out, long long ldo, int nrows, int ncols,
         const int a = oa[i], b = ob[j];
         double acc = 0.0;
         for (int q = 0; q < Q; ++q) {
+            if constexpr (SEP) {
+                double v[8];
+                ex_eval_sep(kinds[q], prm, q, Xa + (long long)i * P, Xb + (long long)j * P,
+                            cols + q * EX_LEAF_COLS, v);
+                acc += Bm[((long long)q * D + a) * D + b] * v[0];
+                continue;
+            }
             const double r = ex_dist(Xa + (long long)i * P, Xb + (long long)j * P, cols + q * EX_MAX_COLS);
             if constexpr (NF == 1) {
                 double v[4];
@@ -262,10 +294,12 @@ k_ex_assemble(double* __restrict__ out, long long ldo, int nrows, int ncols,
 // j = blockIdx.x EX_CR_COLS + threadIdx.x: it reads x_j and ob(j) once, loops over the staged
 // rows and stores out[t][j], consecutive along j across the wave.  Every entry goes through
 // ex_dist / ex_eval (ex_value<NF> past one factor) with the sum over q in k_ex_assemble's order.
-// LDS: rg (P + Q D) + (stage_cols ? EX_CR_COLS ldx : 0) doubles (ex_cross_rows sizes rg).
+// LDS: rg (P + Q D) + (stage_cols ? EX_CR_COLS ldx : 0) doubles (ex_cross_rows sizes rg); SEP
+// (ex_eval_sep) reads the leaves' column table where the others read the kernels', nothing more
+// is staged.
 // ---------------------------------------------------------------------------
 #define EX_CR_COLS 256
-template <int NF>
+template <int NF, bool SEP = false>
 __global__ void __launch_bounds__(EX_CR_COLS)
 k_ex_cross_rows(double* __restrict__ out, long long ldo, int nrows, int ncols, int rg,
                 const double* __restrict__ Xt, const int* __restrict__ ot,
@@ -301,6 +335,12 @@ k_ex_cross_rows(double* __restrict__ out, long long ldo, int nrows, int ncols, i
         const double* bt = sb + (long long)t * QD + b;
         double acc = 0.0;
         for (int q = 0; q < Q; ++q) {
+            if constexpr (SEP) {
+                double v[8];
+                ex_eval_sep(kinds[q], prm, q, xa, xb, cols + q * EX_LEAF_COLS, v);
+                acc += bt[q * D] * v[0];
+                continue;
+            }
             const double r = ex_dist(xa, xb, cols + q * EX_MAX_COLS);
             if constexpr (NF == 1) {
                 double v[4];
@@ -675,9 +715,10 @@ k_ex_sum2(const double* __restrict__ x, int n, double* __restrict__ out) {
 // block 256, LDS (nslot + 1) x 256 doubles.
 // NF == 1 (plain kernels): up to three derivatives from ex_eval, four sums per thread.
 // NF > 1: ex_eval_fact's eight fixed places summed in eight registers, then stored to the slots
-// dslot[q] + p in the derivative order (factors in order, the scale last).
+// dslot[q] + p in the derivative order (factors in order, the scale last).  SEP: the same sums
+// with every leaf on its own distance (ex_eval_sep; cols the table of the leaves).
 // ---------------------------------------------------------------------------
-template <int NF>
+template <int NF, bool SEP = false>
 __global__ void __launch_bounds__(256)
 k_ex_grad_tiles(const double* __restrict__ Kinv, long long n, const double* __restrict__ alpha,
                 const int* __restrict__ tiles, const int* __restrict__ bounds,
@@ -707,7 +748,7 @@ k_ex_grad_tiles(const double* __restrict__ Kinv, long long n, const double* __re
     for (int q = 0; q < Q; ++q) {
         const int kind = kinds[q];
         const double* pq = prm + 4 * q;
-        const int* cq = cols + q * EX_MAX_COLS;
+        const int* cq = cols + q * (SEP ? EX_LEAF_COLS : EX_MAX_COLS);
         if constexpr (NF == 1) {
             double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
             int np = 0;
@@ -737,7 +778,10 @@ k_ex_grad_tiles(const double* __restrict__ Kinv, long long n, const double* __re
                 const int i = r0 + e / EX_T, j = c0 + e % EX_T;
                 if (i >= re || j >= ce || (a == b && j > i)) continue;
                 double v[8];
-                ex_eval_fact<NF>(kind, prm, q, ex_dist(X + (long long)i * P, X + (long long)j * P, cq), v);
+                if constexpr (SEP)
+                    ex_eval_sep(kind, prm, q, X + (long long)i * P, X + (long long)j * P, cq, v);
+                else
+                    ex_eval_fact<NF>(kind, prm, q, ex_dist(X + (long long)i * P, X + (long long)j * P, cq), v);
                 const double m = mw[u];
 #pragma unroll
                 for (int p = 0; p < 8; ++p) s[p] += m * v[p];

@@ -9,6 +9,7 @@ enum { EX_EMPTY = 0, EX_SET, EX_ASSEMBLED, EX_FACTORED, EX_INVERTED };
 struct rl_exact {
     int device = 0, n = 0, P = 0, D = 0, Q = 0, nslot = 0, ncu = 1;
     int maxf = 1;                   // most factors of any kernel (3 with any cosine leaf): 1 runs the kernels' <1> bodies
+    int sep = 0;                    // rl_exact_set_separable: cols holds the leaves' column lists, the kernels run <., true>
     int state = EX_EMPTY;
     double* A = nullptr;            // n x n
     double* X = nullptr;            // n x P
@@ -16,7 +17,7 @@ struct rl_exact {
     int* bounds = nullptr;          // D + 1 row offsets of the outputs
     int* kinds = nullptr;           // descriptors (rl_exact.h: ex_desc; capacity EX_MAX_SLOT kernels)
     double* prm = nullptr;
-    int* cols = nullptr;
+    int* cols = nullptr;            // [Q][EX_MAX_COLS], or [Q][EX_MAX_FACT][EX_MAX_COLS] when sep
     int* dslot = nullptr;
     double* Bm = nullptr;           // Q x D x D
     double* noise = nullptr;        // D
@@ -49,10 +50,13 @@ static int ex_ws(rl_exact* h, size_t doubles) {
     return RL_OK;
 }
 
-// a kernel templated on the factor count, at the handle's: plain sets run <1>
+// a kernel templated on the factor count, at the handle's: plain sets run <1>, separable sets
+// the per-leaf distances
 #define EX_LAUNCH_FACT(h, kern, grid, block, smem, stream, ...)                         \
     do {                                                                                \
-        if ((h)->maxf == 1)                                                             \
+        if ((h)->sep)                                                                   \
+            RL_LAUNCH((kern<EX_MAX_FACT, true>), grid, block, smem, stream, __VA_ARGS__); \
+        else if ((h)->maxf == 1)                                                        \
             RL_LAUNCH(kern<1>, grid, block, smem, stream, __VA_ARGS__);                 \
         else                                                                            \
             RL_LAUNCH(kern<EX_MAX_FACT>, grid, block, smem, stream, __VA_ARGS__);       \
@@ -160,7 +164,7 @@ extern "C" int rl_exact_create(int device, int n, int P, rl_exact** out) {
     RL_HIP(hipMalloc((void**)&h->bounds, (EX_MAX_D + 1) * sizeof(int)));
     RL_HIP(hipMalloc((void**)&h->kinds, EX_MAX_SLOT * sizeof(int)));
     RL_HIP(hipMalloc((void**)&h->prm, 2 * EX_PRM2 * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&h->cols, EX_MAX_SLOT * EX_MAX_COLS * sizeof(int)));
+    RL_HIP(hipMalloc((void**)&h->cols, EX_MAX_SLOT * EX_LEAF_COLS * sizeof(int)));
     RL_HIP(hipMalloc((void**)&h->dslot, EX_MAX_SLOT * sizeof(int)));
     RL_HIP(hipMalloc((void**)&h->Bm, (size_t)EX_MAX_SLOT * EX_MAX_D * EX_MAX_D * sizeof(double)));
     RL_HIP(hipMalloc((void**)&h->noise, EX_MAX_D * sizeof(double)));
@@ -173,6 +177,9 @@ extern "C" int rl_exact_create(int device, int n, int P, rl_exact** out) {
                               hipFuncAttributeMaxDynamicSharedMemorySize,
                               (EX_MAX_SLOT + 1) * 256 * (int)sizeof(double));
     (void)hipFuncSetAttribute((const void*)k_ex_grad_tiles<EX_MAX_FACT>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (EX_MAX_SLOT + 1) * 256 * (int)sizeof(double));
+    (void)hipFuncSetAttribute((const void*)k_ex_grad_tiles<EX_MAX_FACT, true>,
                               hipFuncAttributeMaxDynamicSharedMemorySize,
                               (EX_MAX_SLOT + 1) * 256 * (int)sizeof(double));
     *out = guard.release();
@@ -196,11 +203,15 @@ extern "C" int rl_exact_destroy(rl_exact* h) {
 // parameter groups, [g_0, T_0, c, -] and [g_1, T_1, g_2, T_2]; it runs per kernel where
 // rl_exact_set has always checked the kind, so every error keeps its precedence.  Nothing indexed
 // by q is written past EX_MAX_SLOT kernels: a larger Q only counts, and is refused with the count.
-// `what` names the entry point in messages.
+// `what` names the entry point in messages.  sep: active_cols holds a column list per LEAF,
+// [Q][EX_MAX_FACT][EX_MAX_COLS]; those of a kernel's factors are checked as a kernel's list is
+// (the lists past its last factor are not read) and go to the device in that layout.
 template <class Describe>
 static int ex_set(rl_exact* h, const char* what, const double* X, const int* lens, int D, int Q,
-                  Describe describe, const int* active_cols, const double* B, const double* noise) {
+                  Describe describe, const int* active_cols, const double* B, const double* noise,
+                  bool sep = false) {
     const std::string fn = what;
+    const int stride = sep ? EX_LEAF_COLS : EX_MAX_COLS;
     if (D > EX_MAX_D) return fail(RL_ELIMIT, fn + ": D > 64 outputs");
     long long total = 0;
     for (int d = 0; d < D; ++d) {
@@ -212,7 +223,7 @@ static int ex_set(rl_exact* h, const char* what, const double* X, const int* len
                                    std::to_string(h->n));
     long long nslot = Q;
     int maxf = 1;
-    std::vector<int> descs(EX_MAX_SLOT, 0), dslot(EX_MAX_SLOT, 0), cols((size_t)EX_MAX_SLOT * EX_MAX_COLS, -1);
+    std::vector<int> descs(EX_MAX_SLOT, 0), dslot(EX_MAX_SLOT, 0), cols((size_t)EX_MAX_SLOT * EX_LEAF_COLS, -1);
     std::vector<double> prm(2 * EX_PRM2, 0.0);
     for (int q = 0; q < Q; ++q) {
         int desc = 0;
@@ -232,16 +243,23 @@ static int ex_set(rl_exact* h, const char* what, const double* X, const int* len
                 prm[EX_PRM2 + 4 * q + p] = p1[p];
             }
         }
-        int nc = 0;
-        for (int c = 0; c < EX_MAX_COLS; ++c) {
-            const int col = active_cols[q * EX_MAX_COLS + c];
-            if (col >= h->P) return fail(RL_EINVAL, fn + ": active column beyond P");
-            if (col < 0) break;
-            ++nc;
+        for (int f = 0; f < (sep ? ex_desc_nf(desc) : 1); ++f) {
+            const int* list = active_cols + (size_t)q * stride + f * EX_MAX_COLS;
+            int nc = 0;
+            for (int c = 0; c < EX_MAX_COLS; ++c) {
+                const int col = list[c];
+                if (col >= h->P) return fail(RL_EINVAL, fn + ": active column beyond P");
+                if (col < 0) break;
+                ++nc;
+            }
+            if (nc == 0)
+                return fail(RL_EINVAL, fn + (sep ? ": leaf " + std::to_string(f) + " of kernel " + std::to_string(q) +
+                                                       " without active columns"
+                                                 : std::string(": a kernel without active columns")));
+            if (keep)
+                for (int c = 0; c < EX_MAX_COLS; ++c)
+                    cols[(size_t)q * stride + f * EX_MAX_COLS + c] = c < nc ? list[c] : -1;
         }
-        if (nc == 0) return fail(RL_EINVAL, fn + ": a kernel without active columns");
-        if (keep)
-            for (int c = 0; c < EX_MAX_COLS; ++c) cols[q * EX_MAX_COLS + c] = c < nc ? active_cols[q * EX_MAX_COLS + c] : -1;
     }
     if (nslot > EX_MAX_SLOT)
         return fail(RL_ELIMIT, fn + ": Q + sum of kernel parameters = " + std::to_string(nslot) +
@@ -257,7 +275,7 @@ static int ex_set(rl_exact* h, const char* what, const double* X, const int* len
     RL_HIP(hipMemcpy(h->bounds, bounds.data(), (D + 1) * sizeof(int), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(h->kinds, descs.data(), Q * sizeof(int), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(h->prm, prm.data(), 2 * EX_PRM2 * sizeof(double), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(h->cols, cols.data(), (size_t)Q * EX_MAX_COLS * sizeof(int), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(h->cols, cols.data(), (size_t)Q * stride * sizeof(int), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(h->dslot, dslot.data(), Q * sizeof(int), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(h->Bm, B, (size_t)Q * D * D * sizeof(double), hipMemcpyHostToDevice));
     RL_HIP(hipMemcpy(h->noise, noise, D * sizeof(double), hipMemcpyHostToDevice));
@@ -285,7 +303,8 @@ static int ex_set(rl_exact* h, const char* what, const double* X, const int* len
     h->D = D;
     h->Q = Q;
     h->nslot = (int)nslot;
-    h->maxf = maxf;
+    h->maxf = sep ? EX_MAX_FACT : maxf;
+    h->sep = sep ? 1 : 0;
     h->hbounds = bounds;
     h->state = EX_SET;
     return RL_OK;
@@ -336,6 +355,36 @@ extern "C" int rl_exact_set_factors(rl_exact* h, const double* X, const int* len
         return RL_OK;
     };
     return ex_set(h, "rl_exact_set_factors", X, lens, D, Q, describe, active_cols, B, noise);
+}
+
+extern "C" int rl_exact_set_separable(rl_exact* h, const double* X, const int* lens, int D, int Q,
+                                      const int* nfact, const int* leaf_kinds,
+                                      const double* leaf_params, const int* leaf_cols,
+                                      const int* scaled, const double* scales, const double* B,
+                                      const double* noise) {
+    if (!h || !X || !lens || !nfact || !leaf_kinds || !leaf_params || !leaf_cols || !scaled ||
+        !scales || !B || !noise)
+        return fail(RL_EINVAL, "rl_exact_set_separable: NULL argument");
+    if (D < 1 || Q < 1) return fail(RL_EINVAL, "rl_exact_set_separable: D and Q must be >= 1");
+    auto describe = [&](int q, int* desc, double* p0, double* p1) -> int {
+        const int nf = nfact[q];
+        if (nf < 1 || nf > EX_MAX_FACT)
+            return fail(RL_EINVAL, "rl_exact_set_separable: kernel " + std::to_string(q) + " has " +
+                                       std::to_string(nf) + " factors (1 .. 3)");
+        const int* leaf = leaf_kinds + (size_t)q * EX_MAX_FACT;
+        for (int f = 0; f < nf; ++f) {
+            if (leaf[f] != EX_RBF && leaf[f] != EX_MATERN32 && leaf[f] != EX_STDPERIODIC &&
+                leaf[f] != EX_MATERN52 && leaf[f] != EX_COSINE)
+                return fail(RL_EINVAL, "rl_exact_set_separable: unknown kernel kind " + std::to_string(leaf[f]));
+            double* pf = f == 0 ? p0 : p1 + 2 * (f - 1);
+            pf[0] = leaf_params[((size_t)q * EX_MAX_FACT + f) * 2];
+            pf[1] = leaf_params[((size_t)q * EX_MAX_FACT + f) * 2 + 1];
+        }
+        p0[2] = scaled[q] ? scales[q] : 0.0;
+        *desc = ex_desc(leaf, nf, scaled[q] != 0);
+        return RL_OK;
+    };
+    return ex_set(h, "rl_exact_set_separable", X, lens, D, Q, describe, leaf_cols, B, noise, true);
 }
 
 extern "C" int rl_exact_assemble(rl_exact* h) {

@@ -21,12 +21,80 @@ class StationaryKern:
         """List of dk/dtheta_p arrays, one per parameter."""
         raise NotImplementedError
 
+    # -- evaluation at per-axis lags: `lags` holds one array of absolute coordinate differences
+    #    per active dimension, in sorted order, broadcasting against each other.  A kernel of one
+    #    distance forms the Euclidean norm; Separable hands each factor its own axes
+    def from_lags(self, lags):
+        return self.from_dist(lags_to_dist(lags))
+
+    def kernel_gradient_lags(self, lags):
+        return self.kernel_gradient(lags_to_dist(lags))
+
+    @property
+    def separable(self):
+        """Whether the kernel needs per-axis lags (no single distance determines it)."""
+        return False
+
     def update_gradient(self, grad):
         self.gradient = np.asarray(grad, dtype=float)
 
     @property
     def param_array(self):
         raise NotImplementedError
+
+
+def lags_to_dist(lags):
+    """r = sqrt(sum lags^2), summed in the order given."""
+    return np.sqrt(sum(np.square(np.asarray(g, dtype=float)) for g in lags))
+
+
+class Lags:
+    """Distances that keep their axes: `lags`, one array of absolute coordinate differences per
+    active dimension (sorted order, broadcasting against each other), and `dist`, their
+    Euclidean norm (an array handed in is kept as it is: a model's kernels of one distance then
+    see the array they have always seen).  Accepted wherever the model layers take an array of
+    distances (kernel_values / kernel_gradients below)."""
+
+    def __init__(self, lags, dist=None):
+        self.lags = tuple(np.asarray(g, dtype=float) for g in lags)
+        if not self.lags:
+            raise ValueError('Lags needs at least one axis')
+        self.dist = lags_to_dist(self.lags) if dist is None else dist
+
+    @property
+    def shape(self):
+        return np.shape(self.dist)
+
+    @property
+    def ndim(self):
+        return np.ndim(self.dist)
+
+    @classmethod
+    def zero(cls, naxes):
+        """Lag zero on every axis (k(0): the native variance)."""
+        return cls((np.zeros(()),) * int(naxes), 0)
+
+    @classmethod
+    def between(cls, A, B, dist=None):
+        """Pairwise lags |a_i - b_j| per column of A (na, p) and B (nb, p)."""
+        A, B = np.asarray(A, dtype=float), np.asarray(B, dtype=float)
+        return cls([np.abs(A[:, None, c] - B[None, :, c]) for c in range(A.shape[1])], dist)
+
+
+def kernel_values(k, d):
+    """k at `d`: an array of distances (from_dist -- a Separable raises ValueError there) or a
+    Lags (a separable kernel takes its axes, any other its distance array)."""
+    if isinstance(d, Lags):
+        return k.from_lags(d.lags) if getattr(k, 'separable', False) else k.from_dist(d.dist)
+    return k.from_dist(d)
+
+
+def kernel_gradients(k, d):
+    """kernel_values' rule for the parameter derivatives."""
+    if isinstance(d, Lags):
+        return (k.kernel_gradient_lags(d.lags) if getattr(k, 'separable', False)
+                else k.kernel_gradient(d.dist))
+    return k.kernel_gradient(d)
 
 
 class RBF(StationaryKern):
@@ -49,6 +117,18 @@ class RBF(StationaryKern):
 
     def set_params(self, p):
         self.inv_lengthscale = float(p[0])
+
+    @staticmethod
+    def ard(inv_lengthscales, active_dims):
+        """exp(-sum_i gamma_i d_i^2 / 2), an inverse lengthscale per dimension (automatic
+        relevance determination): the Separable of one RBF per dimension, 2 or 3 of them."""
+        gammas, dims = list(inv_lengthscales), list(active_dims)
+        if len(gammas) != len(dims):
+            raise ValueError('RBF.ard: %d inverse lengthscales for %d dimensions' % (len(gammas), len(dims)))
+        if len(dims) not in (2, 3):
+            raise ValueError('RBF.ard takes 2 or 3 dimensions, got %d' % len(dims))
+        return Separable(*[RBF(g, name='rbf%d' % d, active_dims=[d]) for g, d in zip(gammas, dims)],
+                         name='rbf_ard')
 
 
 class Matern32(StationaryKern):
@@ -148,6 +228,17 @@ class Scaled(StationaryKern):
     def kernel_gradient(self, dists):
         return ([self.scale * g for g in self.k.kernel_gradient(dists)] +
                 [self.k.from_dist(dists)])
+
+    def from_lags(self, lags):
+        return self.scale * self.k.from_lags(lags)
+
+    def kernel_gradient_lags(self, lags):
+        return ([self.scale * g for g in self.k.kernel_gradient_lags(lags)] +
+                [self.k.from_lags(lags)])
+
+    @property
+    def separable(self):
+        return self.k.separable
 
     def update_gradient(self, grad):
         # the reference creates `scale` but never links it (scaled.py:20), so
@@ -250,6 +341,131 @@ class Product(StationaryKern):
                     others = others * v
             grads.extend(g * others for g in f.kernel_gradient(dists))
         return grads
+
+    def _sizes(self):
+        return [len(f.param_array) for f in self.factors]
+
+    def update_gradient(self, grad):
+        grad = np.asarray(grad, dtype=float)
+        self.gradient = grad
+        pos = 0
+        for f, n in zip(self.factors, self._sizes()):
+            f.update_gradient(grad[pos:pos + n])
+            pos += n
+
+    @property
+    def param_array(self):
+        return np.concatenate([f.param_array for f in self.factors])
+
+    def set_params(self, p):
+        pos = 0
+        for f, n in zip(self.factors, self._sizes()):
+            f.set_params(p[pos:pos + n])
+            pos += n
+
+
+class Separable(StationaryKern):
+    """prod_g k_g(|x - x'| over g's own dimensions): every factor a leaf (RBF, Matern32, Matern52,
+    StdPeriodic, Cosine) or a Product of leaves, with an explicit active_dims of its own; the sets
+    are pairwise disjoint and their sorted union is the kernel's active_dims.  At least 2 factors,
+    at most 3 leaves in all.  Parameters and derivatives as Product's: the factors in the order
+    given, each factor's in its own order.  A scale goes outside: Scaled(Separable(...), c).
+    There is no single distance: from_lags / kernel_gradient_lags evaluate it, from_dist and
+    kernel_gradient raise ValueError."""
+
+    MAX_LEAVES = 3
+
+    def __init__(self, *factors, name=None):
+        leaves, seen = 0, {}
+        for f in factors:
+            if isinstance(f, Scaled):
+                raise ValueError('a Scaled factor (%s) in a Separable: put the scale outside, '
+                                 'Scaled(Separable(...), c)' % f.name)
+            if type(f) is Product:
+                leaves += len(f.factors)
+            elif type(f) in (RBF, Matern32, Matern52, StdPeriodic, Cosine):
+                leaves += 1
+            else:
+                raise ValueError('a Separable takes RBF, Matern32, Matern52, StdPeriodic, Cosine and '
+                                 'Product factors, got %s' % type(f).__name__)
+            if f.active_dims is None or len(f.active_dims) == 0:
+                raise ValueError('factor %s of a Separable has no active_dims: every factor names '
+                                 'its own dimensions' % f.name)
+            for d in f.active_dims:
+                if int(d) in seen:
+                    raise ValueError('factors %s and %s of a Separable both act on dimension %d: the '
+                                     'sets must be disjoint' % (seen[int(d)], f.name, int(d)))
+            for d in f.active_dims:
+                seen[int(d)] = f.name
+        if len(factors) < 2:
+            raise ValueError('a Separable takes at least 2 factors, got %d' % len(factors))
+        if leaves > self.MAX_LEAVES:
+            raise ValueError('a Separable takes at most %d leaf kernels in all, got %d'
+                             % (self.MAX_LEAVES, leaves))
+        self.factors = list(factors)
+        for f in self.factors:
+            f.active_dims = tuple(sorted(int(d) for d in f.active_dims))
+        self._dims = tuple(sorted(seen))
+        super().__init__(name or '_x_'.join(f.name for f in self.factors), self._dims)
+
+    @property
+    def active_dims(self):
+        return self._dims
+
+    @active_dims.setter
+    def active_dims(self, value):
+        # (FunctionalKernel.set_input_dim writes the sorted tuple back; the factors fix the set)
+        if value is not None and tuple(sorted(value)) != self._dims:
+            raise ValueError('%s acts on dimensions %s, the union of its factors\': they cannot be '
+                             'set to %s' % (self.name, self._dims, tuple(value)))
+
+    @property
+    def separable(self):
+        return True
+
+    def _no_distance(self):
+        raise ValueError('%s is separable: it has no single distance, evaluate it at per-axis lags '
+                         '(from_lags, kernel_gradient_lags)' % self.name)
+
+    def from_dist(self, dists):
+        self._no_distance()
+
+    def kernel_gradient(self, dists):
+        self._no_distance()
+
+    def _own(self, f, lags):
+        if len(lags) != len(self._dims):
+            raise ValueError('%s acts on %d dimensions, got %d lag arrays'
+                             % (self.name, len(self._dims), len(lags)))
+        return tuple(lags[self._dims.index(d)] for d in f.active_dims)
+
+    def from_lags(self, lags):
+        vals = [f.from_lags(self._own(f, lags)) for f in self.factors]
+        if any(np.ndim(v) == 0 and np.isnan(v) for v in vals):
+            return np.nan       # (StdPeriodic's convention for a vanishing period)
+        out = vals[0]
+        for v in vals[1:]:
+            out = out * v
+        return out
+
+    def kernel_gradient_lags(self, lags):
+        vals = [f.from_lags(self._own(f, lags)) for f in self.factors]
+        grads = []
+        for i, f in enumerate(self.factors):
+            others = 1.0
+            for j, v in enumerate(vals):
+                if j != i:
+                    others = others * v
+            grads.extend(g * others for g in f.kernel_gradient_lags(self._own(f, lags)))
+        return grads
+
+    def leaves(self):
+        """(leaf kernel, its dimensions) in derivative order."""
+        out = []
+        for f in self.factors:
+            for leaf in (f.factors if type(f) is Product else [f]):
+                out.append((leaf, f.active_dims))
+        return out
 
     def _sizes(self):
         return [len(f.param_array) for f in self.factors]

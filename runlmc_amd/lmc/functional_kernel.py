@@ -11,6 +11,8 @@ kernel's ``gradient``."""
 import numpy as np
 import scipy.stats
 
+from ..kern.stationary import kernel_values, kernel_gradients
+
 
 class FunctionalKernel:
     def __init__(self, D=None, lmc_kernels=None, lmc_ranks=None,
@@ -108,17 +110,19 @@ class FunctionalKernel:
         return [q for q in idxs if q < lim]
 
     # -- evaluation on distances (host, O(m) per kernel) -------------------------
+    # an entry of `dists` is an array of distances or a kern.Lags (the distances with their
+    # per-axis lags, which a Separable kernel needs; every other kernel takes its distance array)
     def eval_kernels(self, dists):
         assert self.P
-        return [k.from_dist(dists[k.active_dims]) for k in self._kernels]
+        return [kernel_values(k, dists[k.active_dims]) for k in self._kernels]
 
     def eval_kernels_fixed_dim(self, dists, active_dim):
-        return np.array([self._kernels[q].from_dist(dists)
+        return np.array([kernel_values(self._kernels[q], dists)
                          for q in self.active_dims[active_dim]])
 
     def eval_kernel_gradients(self, dists):
         assert self.P
-        return [k.kernel_gradient(dists[k.active_dims]) for k in self._kernels]
+        return [kernel_gradients(k, dists[k.active_dims]) for k in self._kernels]
 
     # -- parameters -----------------------------------------------------------
     @property

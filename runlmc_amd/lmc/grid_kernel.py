@@ -24,6 +24,11 @@ from ..linalg.diag import Diag
 from ..linalg.sum_matrix import SumMatrix
 from .._native import GridOp, SkiOp, solve_direct, solve_pcg
 from .._lib import as_f64
+from ..kern.stationary import Lags
+
+
+def _distances(grid_dists):
+    return grid_dists if isinstance(grid_dists, Lags) else np.asarray(grid_dists)
 
 
 def choose_ktype(fk, active_dim):
@@ -110,7 +115,8 @@ class GridKernel(Matrix):
         self.ktype = ktype
         self.active_dim = active_dim
         fk = functional_kernel
-        grid_dists = np.asarray(grid_dists)
+        # (a kern.Lags -- the distances with the grid's per-axis lags -- passes as it is)
+        grid_dists = _distances(grid_dists)
         if grid_dists.ndim > 2:
             raise NotImplementedError(
                 'device GridKernel supports 1-D and 2-D grids')
@@ -136,7 +142,7 @@ class GridKernel(Matrix):
         spectra and factors (rl_gridop_set_lmc), keep W on the device."""
         fk = functional_kernel
         kidx = fk.active_dims[self.active_dim]
-        tops = as_f64(fk.eval_kernels_fixed_dim(np.asarray(grid_dists),
+        tops = as_f64(fk.eval_kernels_fixed_dim(_distances(grid_dists),
                                                 self.active_dim)).reshape(len(kidx), -1)
         self._set(fk, kidx, tops)
         self.version += 1

@@ -33,6 +33,7 @@ import torch
 
 from ..approx.interpolation import autogrid, multi_interpolant
 from ..approx.iterative import Iterative
+from ..kern.stationary import Lags, kernel_values
 from ..lmc.grid_kernel import gen_grid_kernel
 from ..lmc.likelihood import ApproxLMCLikelihood, ExactLMCLikelihood
 from ..lmc.metrics import Metrics
@@ -106,10 +107,14 @@ class InterpolatedLLGP:
         self._functional_kernel.set_input_dim(self.input_dim)
         if any(len(ad) > 2 for ad in functional_kernel.active_dims):
             raise NotImplementedError(
-                'kernels may act on one or two input dimensions each')
+                'kernels may act on one or two input dimensions each (a Separable kernel over '
+                'three is usable through ExactLMCLikelihood only)')
         self.y = np.hstack(self.Ys)
         self.kernel = None
         self.dists, self.interpolants, self.grid_axes = {}, {}, {}
+        # lags[ad]: dists[ad] together with the per-axis mesh it is the norm of (kern.Lags): what
+        # the layers below are handed, so that a Separable kernel finds its axes
+        self.lags = {}
         self._generate_grids(lo, hi, m)
         self.metrics = Metrics() if metrics else None
         self._device_index = device_index
@@ -166,6 +171,7 @@ class InterpolatedLLGP:
             # grid (interpolated_llgp.py:425-432)
             mesh = np.meshgrid(*[a - a[0] for a in axes], indexing='ij')
             self.dists[ad] = np.sqrt(sum(np.square(g) for g in mesh))
+            self.lags[ad] = Lags(mesh, self.dists[ad])
             W = multi_interpolant(Xs, *self.grid_axes[ad])
             WT = W.transpose().tocsr()
             WT.sort_indices()
@@ -236,15 +242,15 @@ class InterpolatedLLGP:
         lens = [len(Y) for Y in self.Ys]
         if self._K is None:
             self._K, self._grid_kernels = gen_grid_kernel(
-                fk, self.dists, self.interpolants, lens,
+                fk, self.lags, self.interpolants, lens,
                 device_index=self._device_index)
         else:
             # same grid and interpolants: only spectra, factors and noise change
             for ad, gk in self._grid_kernels.items():
-                gk.update(fk, self.dists[ad])
+                gk.update(fk, self.lags[ad])
             self._K.update_noise(fk.noise, lens)
         self.kernel = ApproxLMCLikelihood(
-            fk, self._K, self.dists, self.interpolants, self.Ys,
+            fk, self._K, self.lags, self.interpolants, self.Ys,
             self._deriv_service)
         self.kernel._grid_kernels = self._grid_kernels
         fk.update_gradient(self.kernel)
@@ -345,7 +351,7 @@ class InterpolatedLLGP:
         fk = self._functional_kernel
         coregs = np.column_stack([np.square(a).sum(axis=0) for a in fk.coreg_vecs])
         coregs = coregs + np.column_stack(fk.coreg_diags)
-        zero = {ad: 0 for ad in fk.active_dims}
+        zero = {ad: Lags.zero(len(ad)) for ad in fk.active_dims}
         k0 = np.array(fk.eval_kernels(zero), dtype=float)
         return coregs.dot(k0).reshape(-1) + fk.noise
 
@@ -358,10 +364,14 @@ class InterpolatedLLGP:
         B = np.vstack(self.Xs)
         dist = {ad: sdist.cdist(A[:, list(ad)], B[:, list(ad)])
                 for ad in fk.active_dims}
+        for k in fk.kernels:
+            ad = k.active_dims
+            if k.separable and not isinstance(dist[ad], Lags):
+                dist[ad] = Lags.between(A[:, list(ad)], B[:, list(ad)], dist[ad])
         ro, co = np.repeat(np.arange(fk.D), rl), np.repeat(np.arange(fk.D), cl)
         K = np.zeros((sum(rl), sum(cl)))
         for Bq, k in zip(fk.coreg_mats(), fk.kernels):
-            K += Bq[np.ix_(ro, co)] * k.from_dist(dist[k.active_dims])
+            K += Bq[np.ix_(ro, co)] * kernel_values(k, dist[k.active_dims])
         return K
 
     def _light_exact(self):
