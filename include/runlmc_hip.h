@@ -46,7 +46,8 @@ typedef struct rl_exact rl_exact;
  * rl_pathwise_residual, the function draws; 8: rl_ski_inverse_diag, rl_ski_precond_apply,
  * rl_diag_accumulate and rl_loo_reduce, leave-one-out cross-validation; callers
  * built against an older version must be rebuilt; rl_exact_set_factors joined version 8
- * without a bump: no declared signature changed).  A binding
+ * without a bump: no declared signature changed, and so did rl_gridop_create_3d and
+ * rl_gridop_info_3d, the three-dimensional grids).  A binding
  * compares rl_abi_version() with the RL_ABI_VERSION it was written against before its
  * first call (runlmc_amd/_lib.py does) instead of finding out through shifted arguments. */
 #define RL_ABI_VERSION 8
@@ -82,6 +83,31 @@ int rl_gridop_create(int device, int D, int m, int max_tops, rl_gridop** out);
  * (N2 = 1024: D >= 8; 2048: D >= 4; 4096: D >= 2) runs through the one-output
  * handle and the mix pass described above, as D > 16 does.                    */
 int rl_gridop_create_2d(int device, int D, int m1, int m2, int max_tops, rl_gridop** out);
+/* Same for a three-dimensional m0 x m1 x m2 grid: T_q is a three-level block-Toeplitz
+ * matrix, BTTB(top, (m0, m1, m2)) (bttb.py:91-148 with three sizes; grid index
+ * (i0*m1 + i1)*m2 + i2, m = m0*m1*m2 points per output).  The leading axis is embedded
+ * in a circulant of N0 = pow2 >= 2 m0 (>= 4) points; a real transform along it
+ * (csrc/rl_lead.h) turns the product into F = N0/2 + 1 two-dimensional products over
+ * (m1, m2), one per leading frequency, each run by a complete rl_gridop_create_2d
+ * operator the handle owns (its real top rows are sum_j c_q[j] cos(2 pi f j / N0), set
+ * on the host in fp64 by rl_gridop_set_*), on the real and the imaginary slab as two
+ * ordinary vectors; the inverse transform follows.  All on the caller's stream, in order.
+ * Every product entry point is unchanged; rl_gridop_info reports the inner
+ * (L, N1, N2, colsA, rowsB).  The structured forms do not exist on these grids:
+ * rl_gridop_form reports rank 0, rl_gridop_top_forms 0 for every row,
+ * rl_gridop_project / rl_gridop_spectrum_host answer RL_ELIMIT, rl_ski_factor reports
+ * available = 0, rl_sampler_create RL_ELIMIT.
+ * Limits (RL_ELIMIT from host checks before any launch): m0 <= 64 -- put the shortest
+ * axis first --, the two-dimensional limits above on (m1, m2), m0*m1*m2 <= 2^27.
+ * Workspace: 2 F 2 nvec D m1 m2 doubles and the children's own at 2 nvec vectors,
+ * allocated by the first product of that many vectors outside a stream capture
+ * (inside one an unreserved workspace is RL_EINVAL, never an allocation).       */
+int rl_gridop_create_3d(int device, int D, int m0, int m1, int m2, int max_tops,
+                        rl_gridop** out);
+/* Leading axis of a three-dimensional handle: its extent, its embedding length and the
+ * number of leading frequencies (all 0 for one- and two-dimensional handles; any
+ * pointer may be NULL).                                                         */
+int rl_gridop_info_3d(const rl_gridop* g, int* m0, int* N0, int* F);
 int rl_gridop_destroy(rl_gridop* g);
 /* L = N1*N2 and tile parameters actually chosen (any pointer may be NULL). */
 int rl_gridop_info(const rl_gridop* g, int* L, int* N1, int* N2, int* colsA, int* rowsB);

@@ -31,8 +31,10 @@ _SIGNATURES = {
     'rl_device_count': [_c_int_p],
     'rl_gridop_create': [_i, _i, _i, _i, ctypes.POINTER(_vp)],
     'rl_gridop_create_2d': [_i, _i, _i, _i, _i, ctypes.POINTER(_vp)],
+    'rl_gridop_create_3d': [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_vp)],
     'rl_gridop_destroy': [_vp],
     'rl_gridop_info': [_vp, _c_int_p, _c_int_p, _c_int_p, _c_int_p, _c_int_p],
+    'rl_gridop_info_3d': [_vp, _c_int_p, _c_int_p, _c_int_p],
     'rl_gridop_form': [_vp, _c_int_p, ctypes.POINTER(ctypes.c_longlong)],
     'rl_gridop_set_form_gate': [_vp, ctypes.c_longlong],
     'rl_gridop_top_forms': [_vp, _c_int_p, _c_int_p],

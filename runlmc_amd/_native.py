@@ -36,7 +36,8 @@ class GridOp:
 
     def __init__(self, D, m, max_tops, device_index=0, lib=None, sizes=None):
         """`m` grid points per output; `sizes=(m1, m2)` (m1*m2 == m) makes the
-        kernel matrices BTTB on a two-dimensional grid."""
+        kernel matrices BTTB on a two-dimensional grid, `sizes=(m0, m1, m2)` on a
+        three-dimensional one (leading axis of at most 64 points)."""
         self.lib = lib or _lib.get_library()
         self.D, self.m, self.max_tops = int(D), int(m), int(max_tops)
         self.device = self.lib.torch_device(device_index)
@@ -52,12 +53,23 @@ class GridOp:
             self.lib.call('rl_gridop_create_2d', device_index, self.D,
                           self.sizes[0], self.sizes[1], self.max_tops,
                           ctypes.byref(self._h))
+        elif len(self.sizes) == 3:
+            if self.sizes[0] * self.sizes[1] * self.sizes[2] != self.m:
+                raise ValueError('sizes %s do not multiply to m = %d' % (self.sizes, self.m))
+            self.lib.call('rl_gridop_create_3d', device_index, self.D,
+                          self.sizes[0], self.sizes[1], self.sizes[2], self.max_tops,
+                          ctypes.byref(self._h))
         else:
             raise NotImplementedError(
-                'grids of more than two dimensions have no device path')
+                'grids of more than three dimensions have no device path')
         info = [ctypes.c_int() for _ in range(5)]
         self.lib.call('rl_gridop_info', self._h, *[ctypes.byref(i) for i in info])
         self.L, self.N1, self.N2, self.colsA, self.rowsB = [i.value for i in info]
+        # three-dimensional grids: leading extent, its embedding length, leading frequencies
+        # (the five values above are then those of the inner two-dimensional products)
+        lead = [ctypes.c_int() for _ in range(3)]
+        self.lib.call('rl_gridop_info_3d', self._h, *[ctypes.byref(i) for i in lead])
+        self.m0, self.N0, self.F = [i.value for i in lead]
         self.Q = 0
 
     def __del__(self):

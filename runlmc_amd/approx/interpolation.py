@@ -94,6 +94,46 @@ def interp_bicubic(gridx, gridy, samples):
                                    shape=(n, mx * my)).tocsr()
 
 
+def interp_tricubic(gridx, gridy, gridz, samples):
+    """n x (mx*my*mz) CSR matrix with 64 taps per row: the tensor product of
+    the three axes' cubic-convolution weights (interp_cubic's taps along each
+    axis; clamped taps are summed).  Grid index = (ix * my + iy) * mz + iz,
+    the order of np.meshgrid(indexing='ij')."""
+    grids = [np.asarray(g) for g in (gridx, gridy, gridz)]
+    samples = np.asarray(samples)
+    mx, my, mz = (g.size for g in grids)
+    n = samples.shape[0]
+    if n == 0:
+        return scipy.sparse.csr_matrix((0, mx * my * mz), dtype=float)
+    for name, grid in zip(('gridx', 'gridy', 'gridz'), grids):
+        if grid.ndim != 1:
+            raise ValueError('{} dim {} should be 1'.format(name, grid.ndim))
+        if grid.size < 4:
+            raise ValueError('grid size {} must be >=4'.format(grid.size))
+    if samples.ndim != 2 or samples.shape[1] != 3:
+        raise ValueError('expecting 3d samples, got shape {}'.format(samples.shape))
+    for axis, grid in enumerate(grids):
+        col = samples[:, axis]
+        if col.min() <= grid[0] or col.max() >= grid[-1]:
+            _LOG.warning('%s range of samples [%f, %f] outside grid range [%f, %f]',
+                         'xyz'[axis], col.min(), col.max(), grid[0], grid[-1])
+    shifts = np.array([-2, -1, 0, 1])
+
+    def taps(grid, coords):
+        pos = (coords - grid[0]) / (grid[1] - grid[0])
+        left = np.floor(pos)
+        idx = np.clip(left[:, None] - shifts[None, :], 0, len(grid) - 1).astype(np.int64)
+        return idx, cubic_kernel((pos - left)[:, None] + shifts[None, :])
+
+    (ix, wx), (iy, wy), (iz, wz) = (taps(g, samples[:, a]) for a, g in enumerate(grids))
+    cols = ((ix[:, :, None, None] * my + iy[:, None, :, None]) * mz
+            + iz[:, None, None, :]).reshape(n, 64)
+    vals = (wx[:, :, None, None] * wy[:, None, :, None] * wz[:, None, None, :]).reshape(n, 64)
+    rows = np.repeat(np.arange(n), 64)
+    return scipy.sparse.coo_matrix((vals.ravel(), (rows, cols.ravel())),
+                                   shape=(n, mx * my * mz)).tocsr()
+
+
 def multi_interpolant(Xs, *inducing_grids):
     """Block-diagonal interpolant over all outputs: (sum_d n_d) x (D m) CSR
     with int32 indices (reference interpolation.py:119-176)."""
@@ -103,8 +143,10 @@ def multi_interpolant(Xs, *inducing_grids):
     elif Xs[0].shape[1] == 2:
         blocks = [interp_bicubic(inducing_grids[0], inducing_grids[1], np.asarray(X))
                   for X in Xs]
+    elif Xs[0].shape[1] == 3:
+        blocks = [interp_tricubic(*inducing_grids[:3], np.asarray(X)) for X in Xs]
     else:
-        raise NotImplementedError('inputs of more than two dimensions')
+        raise NotImplementedError('inputs of more than three dimensions')
     W = scipy.sparse.block_diag(blocks, format='csr')
     W.sort_indices()
     W.indices = W.indices.astype(np.int32)

@@ -81,6 +81,10 @@ class GridSampler:
                  forms=None):
         op = getattr(grid_kernel, '_op', grid_kernel)
         self.grid = op
+        if op.sizes is not None and len(op.sizes) > 2:
+            raise NotImplementedError(
+                'no function draws on a 3-D grid: the sampler embeds one- and two-dimensional '
+                'grids only')
         kernels, coreg_vecs, coreg_diags = list(kernels), list(coreg_vecs), list(coreg_diags)
         eye = getattr(grid_kernel, '_eye', 0)
         if eye:

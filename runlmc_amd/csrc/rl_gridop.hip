@@ -2,6 +2,7 @@
 // (transform kernels, polynomial-subspace form, recursive filters), products (see
 // include/runlmc_hip.h; one of the three translation units of librunlmc_hip.so, rl_host.h).
 #include "rl_host.h"
+#include "rl_lead.h"
 
 // ---------------------------------------------------------------------------
 // errors
@@ -420,6 +421,8 @@ static int launch1p(rl_gridop* g, int D, unsigned pairs, hipStream_t st, const d
 
 
 static size_t lr_min_elements(const rl_gridop* g);
+static int lead_reserve(rl_gridop* g, int nvec);
+static int lead_mvm(rl_gridop* g, int q, const double* X, double* Y, int nvec, hipStream_t stream);
 static int gridop_create_impl(int device, int D, int m, int m1, int m2, int max_tops,
                               rl_gridop** out);
 
@@ -436,6 +439,67 @@ extern "C" int rl_gridop_create_2d(int device, int D, int m1, int m2, int max_to
     }
     if ((long)m1 * m2 > (1L << 27)) return fail(RL_ELIMIT, "rl_gridop_create_2d: grid too large");
     return gridop_create_impl(device, D, m1 * m2, m1, m2, max_tops, out);
+}
+
+// 3-D grid: one complete 2-D operator per leading frequency (rl_gridop::lead, rl_lead.h)
+extern "C" int rl_gridop_create_3d(int device, int D, int m0, int m1, int m2, int max_tops,
+                                   rl_gridop** out) {
+    if (!out) return fail(RL_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (m0 < 1 || m1 < 1 || m2 < 1)
+        return fail(RL_EINVAL, "rl_gridop_create_3d: m0, m1, m2 must be >= 1");
+    if (D < 1 || max_tops < 1)
+        return fail(RL_EINVAL, "rl_gridop_create_3d: D, max_tops must be >= 1");
+    if (m0 > RL_LEAD_MAX_M0)
+        return fail(RL_ELIMIT, "rl_gridop_create_3d: the leading axis of a 3-D grid holds at most 64 "
+                               "points (put the shortest axis first)");
+    if ((long)m0 * m1 * m2 > (1L << 27) || (long)m1 * m2 > (1L << 27))
+        return fail(RL_ELIMIT, "rl_gridop_create_3d: grid too large");
+    RL_HIP(hipSetDevice(device));
+    rl_gridop* g = new rl_gridop;
+    HandleGuard<rl_gridop, rl_gridop_destroy> guard(g);
+    g->kn = read_knobs();
+    g->device = device;
+    g->D = D;
+    g->m = m0 * m1 * m2;
+    g->max_tops = max_tops;
+    g->geo = Geom{g->m, m1, m2};
+    g->lead = true;
+    g->m0 = m0;
+    g->N0 = 4;
+    while (g->N0 < 2 * m0) g->N0 *= 2;
+    const int F = g->N0 / 2 + 1;
+    g->kids.assign(F, nullptr);
+    for (int f = 0; f < F; ++f)
+        RL_TRY(gridop_create_impl(device, D, m1 * m2, m1, m2, max_tops, &g->kids[f]));
+    const rl_gridop* k0 = g->kids[0];
+    g->L = k0->L;
+    g->N1 = k0->N1;
+    g->N2 = k0->N2;
+    g->colsA = k0->colsA;
+    g->rowsB = k0->rowsB;
+    g->chunk_pairs = k0->chunk_pairs;
+    g->max_fac = max_tops * D;
+    std::vector<double> tw((size_t)g->N0);          // exp(-2 pi i k / N0), k < N0 / 2
+    for (int k = 0; k < g->N0 / 2; ++k) {
+        const double a = -2.0 * M_PI * (double)k / (double)g->N0;
+        tw[2 * k] = std::cos(a);
+        tw[2 * k + 1] = std::sin(a);
+    }
+    // (exact at the quarter turns, so that N0 = 4 is exact arithmetic)
+    tw[0] = 1.0; tw[1] = 0.0;
+    tw[2 * (g->N0 / 4)] = 0.0; tw[2 * (g->N0 / 4) + 1] = -1.0;
+    RL_TRY(upload(&g->lead_tw, tw));
+    *out = guard.release();
+    return RL_OK;
+}
+
+extern "C" int rl_gridop_info_3d(const rl_gridop* g, int* m0, int* N0, int* F) {
+    if (!g) return fail(RL_EINVAL, "gridop is NULL");
+    if (m0) *m0 = g->m0;
+    if (N0) *N0 = g->N0;
+    if (F) *F = g->lead ? g->N0 / 2 + 1 : 0;
+    return RL_OK;
 }
 
 static int gridop_create_impl(int device, int D, int m, int m1, int m2, int max_tops,
@@ -638,6 +702,10 @@ extern "C" int rl_gridop_destroy(rl_gridop* g) {
     if (!g) return RL_OK;
     (void)hipSetDevice(g->device);
     if (g->child) (void)rl_gridop_destroy(g->child);
+    for (rl_gridop* k : g->kids) (void)rl_gridop_destroy(k);
+    if (g->lead_tw) (void)hipFree(g->lead_tw);
+    if (g->lead_x) (void)hipFree(g->lead_x);
+    if (g->lead_y) (void)hipFree(g->lead_y);
     if (g->wide_B) (void)hipFree(g->wide_B);
     if (g->wide_Z) (void)hipFree(g->wide_Z);
     void* ptrs[] = {g->tw1, g->tw2, g->twlo, g->twhi, g->freq1, g->tops, g->spec,
@@ -670,6 +738,11 @@ extern "C" int rl_gridop_info(const rl_gridop* g, int* L, int* N1, int* N2, int*
 
 extern "C" int rl_gridop_form(const rl_gridop* gc, int* rank, long long* min_elements) {
     if (!gc) return fail(RL_EINVAL, "gridop is NULL");
+    if (gc->lead) {                 // 3-D grid: transform kernels only
+        if (rank) *rank = 0;
+        if (min_elements) *min_elements = 0;
+        return RL_OK;
+    }
     if (gc->wide) {
         // (the child's gate counts ITS elements, nvec * D rows of m points: the same number)
         return rl_gridop_form(gc->child, rank, min_elements);
@@ -683,6 +756,13 @@ extern "C" int rl_gridop_form(const rl_gridop* gc, int* rank, long long* min_ele
 
 extern "C" int rl_gridop_top_forms(const rl_gridop* gc, int* forms, int* structured) {
     if (!gc) return fail(RL_EINVAL, "gridop is NULL");
+    if (gc->lead) {                 // 3-D grid: every row on the transform kernels
+        if (gc->Q < 1) return fail(RL_EINVAL, "grid operator has no parameters yet");
+        if (forms)
+            for (int q = 0; q < gc->Q; ++q) forms[q] = 0;
+        if (structured) *structured = 0;
+        return RL_OK;
+    }
     if (gc->wide) {
         // every top runs alone (single-top products of the child): each in its own form
         RL_TRY(rl_gridop_top_forms(gc->child, forms, nullptr));
@@ -706,6 +786,12 @@ extern "C" int rl_gridop_top_forms(const rl_gridop* gc, int* forms, int* structu
 extern "C" int rl_gridop_form_stats(const rl_gridop* gc, int q, double* out4) {
     if (!gc || !out4) return fail(RL_EINVAL, "rl_gridop_form_stats: NULL argument");
     if (gc->wide) return rl_gridop_form_stats(gc->child, q, out4);
+    if (gc->lead) {                 // 3-D grid: no row is ever a candidate
+        if (gc->Q < 1) return fail(RL_EINVAL, "grid operator has no parameters yet");
+        if (q < 0 || q >= gc->Q) return fail(RL_EINVAL, "rl_gridop_form_stats: no such top row");
+        for (int k = 0; k < 4; ++k) out4[k] = 0.0;
+        return RL_OK;
+    }
     rl_gridop* g = const_cast<rl_gridop*>(gc);      // (runs the pending verification)
     if (g->Q < 1) return fail(RL_EINVAL, "grid operator has no parameters yet");
     if (q < 0 || q >= g->Q) return fail(RL_EINVAL, "rl_gridop_form_stats: no such top row");
@@ -718,6 +804,7 @@ extern "C" int rl_gridop_form_stats(const rl_gridop* gc, int q, double* out4) {
 extern "C" int rl_gridop_set_form_gate(rl_gridop* g, long long min_elements) {
     if (!g) return fail(RL_EINVAL, "gridop is NULL");
     if (g->wide) return rl_gridop_set_form_gate(g->child, min_elements);
+    if (g->lead) return RL_OK;      // 3-D grid: no structured form to gate
     g->lr_min = min_elements < 0 ? lr_min_elements(g) : (size_t)min_elements;
     return RL_OK;
 }
@@ -845,11 +932,56 @@ static int wide_set(rl_gridop* g, int Q, const double* tops, const std::vector<d
     return RL_OK;
 }
 
+// 3-D grid: the F Q real rows  T^_q[f] = t_q[0] + 2 sum_{j >= 1} t_q[j] cos(2 pi f j / N0)
+// (the cosine transform of the mirrored embedding of the leading axis, oracle/operators.py:
+// circulant_embed), host [F][Q][m1 m2], in fp64 with the angle reduced mod N0 exactly
+static std::vector<double> lead_rows(const rl_gridop* g, int Q, const double* tops) {
+    const int F = g->N0 / 2 + 1, N0 = g->N0, m0 = g->m0;
+    const size_t M = (size_t)g->m / m0;
+    std::vector<double> cs((size_t)N0);
+    for (int k = 0; k < N0; ++k) cs[k] = std::cos(2.0 * M_PI * (double)k / (double)N0);
+    cs[0] = 1.0;
+    cs[N0 / 4] = 0.0;
+    cs[N0 / 2] = -1.0;
+    cs[3 * N0 / 4] = 0.0;
+    std::vector<double> rows((size_t)F * Q * M);
+    for (int f = 0; f < F; ++f)
+        for (int q = 0; q < Q; ++q) {
+            double* dst = rows.data() + ((size_t)f * Q + q) * M;
+            const double* t = tops + (size_t)q * g->m;
+            for (size_t i = 0; i < M; ++i) dst[i] = t[i];
+            for (int j = 1; j < m0; ++j) {
+                const double c2 = 2.0 * cs[(size_t)((long)f * j % N0)];
+                const double* tj = t + (size_t)j * M;
+                for (size_t i = 0; i < M; ++i) dst[i] += c2 * tj[i];
+            }
+        }
+    return rows;
+}
+
+// ... and every child set with its Q rows and the caller's couplings, unchanged.  A failure
+// leaves the handle without parameters.
+static int lead_set(rl_gridop* g, int Q, const double* tops,
+                    const std::function<int(rl_gridop*, const double*)>& set_child) {
+    g->Q = 0;
+    ++g->param_ver;
+    const std::vector<double> rows = lead_rows(g, Q, tops);
+    const size_t M = (size_t)g->m / g->m0;
+    for (size_t f = 0; f < g->kids.size(); ++f)
+        RL_TRY(set_child(g->kids[f], rows.data() + f * Q * M));
+    g->Q = Q;
+    return RL_OK;
+}
+
 extern "C" int rl_gridop_set_lmc(rl_gridop* g, int Q, const double* tops, const int* ranks,
                                  const double* coreg_vecs, const double* coreg_diags) {
     RL_TRY(set_check(g, Q, tops));
     if (!ranks || !coreg_diags) return fail(RL_EINVAL, "rl_gridop_set_lmc: NULL argument");
     const int D = g->D;
+    if (g->lead)
+        return lead_set(g, Q, tops, [&](rl_gridop* k, const double* rows) {
+            return rl_gridop_set_lmc(k, Q, rows, ranks, coreg_vecs, coreg_diags);
+        });
     if (g->wide) {
         std::vector<double> B((size_t)Q * D * D, 0.0);
         size_t wrow = 0;
@@ -949,6 +1081,10 @@ extern "C" int rl_gridop_set_dense(rl_gridop* g, int Q, const double* tops, cons
     RL_TRY(set_check(g, Q, tops));
     if (!B) return fail(RL_EINVAL, "rl_gridop_set_dense: B is NULL");
     const int D = g->D;
+    if (g->lead)
+        return lead_set(g, Q, tops, [&](rl_gridop* k, const double* rows) {
+            return rl_gridop_set_dense(k, Q, rows, B);
+        });
     if (g->wide) {
         for (int q = 0; q < Q; ++q)
             for (int i = 0; i < D; ++i)
@@ -2365,7 +2501,7 @@ int lr_ensure(rl_gridop* g) {
 int lr_all_coeffs(rl_gridop* g, int R, std::vector<double>* hC, std::vector<char>* exact,
                   std::vector<double>* captured) {
     const int D = g->D, m = g->m, Q = g->Q;
-    if (g->wide || !g->lr_try || Q < 1) return fail(RL_ELIMIT, "no polynomial basis on this grid");
+    if (g->wide || g->lead || !g->lr_try || Q < 1) return fail(RL_ELIMIT, "no polynomial basis on this grid");
     if (R != 24 && R != 32 && R != 36 && R != 40 && R != 48) return fail(RL_EINVAL, "bad basis size");
     RL_HIP(hipSetDevice(g->device));
     RL_TRY(lr_ensure(g));
@@ -2495,6 +2631,90 @@ bool stream_capturing(hipStream_t stream) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     return stream != nullptr && hipStreamIsCapturing(stream, &cs) == hipSuccess &&
            cs != hipStreamCaptureStatusNone;
+}
+
+// ---------------------------------------------------------------------------
+// 3-D grid (rl_gridop::lead, rl_lead.h): k_lead_fwd, one child product per leading
+// frequency, k_lead_inv -- a serial chain on the caller's stream
+// ---------------------------------------------------------------------------
+// workspace of a product of nvec vectors: the two transformed batches and every child's own
+// at 2 nvec vectors
+static int lead_reserve(rl_gridop* g, int nvec) {
+    if (nvec < 1) return RL_OK;
+    if (g->lead_cap < (size_t)nvec) {
+        const size_t F = g->kids.size(), M = (size_t)g->m / g->m0;
+        const size_t need = F * 2 * (size_t)nvec * g->D * M;
+        if (g->lead_x) RL_HIP(hipFree(g->lead_x));
+        if (g->lead_y) RL_HIP(hipFree(g->lead_y));
+        g->lead_x = g->lead_y = nullptr;
+        g->lead_cap = 0;
+        RL_HIP(hipMalloc((void**)&g->lead_x, need * sizeof(double)));
+        RL_HIP(hipMalloc((void**)&g->lead_y, need * sizeof(double)));
+        g->lead_cap = (size_t)nvec;
+    }
+    // (a child's workspace only grows: the middle frequencies take 2 nvec vectors, the two
+    // real-only ones nvec)
+    for (rl_gridop* k : g->kids) RL_TRY(gridop_prepare(k, 2 * nvec));
+    return RL_OK;
+}
+
+template <int N0>
+static void lead_launch(rl_gridop* g, bool inverse, const double* src, double* dst, int nvec,
+                        hipStream_t st) {
+    const long long M = g->m / g->m0, ncol = (long long)nvec * g->D * M;
+    const int thr = rl_lead_threads(N0);
+    const dim3 grid((unsigned)((ncol + thr - 1) / thr)), blk(thr);
+    if (inverse)
+        RL_LAUNCH(k_lead_inv<N0>, grid, blk, rl_lead_inv_lds(N0), st, src, g->m0, M, ncol,
+                  RL_KCONST(g->lead_tw), dst);
+    else
+        RL_LAUNCH(k_lead_fwd<N0>, grid, blk, 0, st, src, g->m0, M, ncol, RL_KCONST(g->lead_tw), dst);
+}
+
+static int lead_transform(rl_gridop* g, bool inverse, const double* src, double* dst, int nvec,
+                          hipStream_t st) {
+    switch (g->N0) {
+        case 4: lead_launch<4>(g, inverse, src, dst, nvec, st); break;
+        case 8: lead_launch<8>(g, inverse, src, dst, nvec, st); break;
+        case 16: lead_launch<16>(g, inverse, src, dst, nvec, st); break;
+        case 32: lead_launch<32>(g, inverse, src, dst, nvec, st); break;
+        case 64: lead_launch<64>(g, inverse, src, dst, nvec, st); break;
+        case 128: lead_launch<128>(g, inverse, src, dst, nvec, st); break;
+        default: return fail(RL_ELIMIT, "3-D grid: no leading-axis transform of this length");
+    }
+    return RL_OK;
+}
+
+// the operator (q < 0) or one top row applied to every output block (q >= 0)
+static int lead_mvm(rl_gridop* g, int q, const double* X, double* Y, int nvec, hipStream_t stream) {
+    if (nvec < 0) return fail(RL_EINVAL, "nvec < 0");
+    if (nvec == 0) return RL_OK;
+    if (!X || !Y) return fail(RL_EINVAL, "X or Y is NULL");
+    if (X == Y) return fail(RL_EINVAL, "X and Y may not alias");
+    if (g->Q < 1) return fail(RL_EINVAL, "grid operator has no parameters yet");
+    // (the grid of a transform launch: one lane per column)
+    if ((size_t)nvec * g->D * ((size_t)g->m / g->m0) > ((size_t)1 << 36))
+        return fail(RL_ELIMIT, "3-D grid: batch too large for one product");
+    RL_HIP(hipSetDevice(g->device));
+    if (g->lead_cap < (size_t)nvec) {
+        if (stream_capturing(stream))
+            return fail(RL_EINVAL, "3-D grid: workspace not reserved before a capture");
+        RL_TRY(lead_reserve(g, nvec));
+    }
+    trace_once("grid product: 3-D grid (k_lead_fwd / one 2-D product per leading frequency / k_lead_inv)");
+    const size_t slab = 2 * (size_t)nvec * g->D * ((size_t)g->m / g->m0);
+    const int F = (int)g->kids.size();
+    RL_TRY(lead_transform(g, false, X, g->lead_x, nvec, stream));
+    for (int f = 0; f < F; ++f) {
+        const int nv = (f == 0 || f == F - 1) ? nvec : 2 * nvec;
+        const double* xf = g->lead_x + (size_t)f * slab;
+        double* yf = g->lead_y + (size_t)f * slab;
+        if (q < 0) RL_TRY(rl_gridop_mvm(g->kids[f], xf, yf, nv, stream));
+        else RL_TRY(rl_gridop_mvm_top(g->kids[f], q, xf, yf, nv, stream));
+    }
+    RL_TRY(lead_transform(g, true, g->lead_y, Y, nvec, stream));
+    RL_HIP(hipGetLastError());
+    return RL_OK;
 }
 
 static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, double* Y, int nvec,
@@ -2665,6 +2885,7 @@ static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, doub
 
 extern "C" int rl_gridop_mvm(rl_gridop* g, const double* X, double* Y, int nvec, void* stream) {
     if (!g) return fail(RL_EINVAL, "gridop is NULL");
+    if (g->lead) return lead_mvm(g, -1, X, Y, nvec, (hipStream_t)stream);
     if (g->wide) return wide_mvm(g, X, Y, nvec, (hipStream_t)stream);
     MixParams mp{g->Q, g->nfac, g->spec, g->facA, g->facW, g->facQ, g->kappa,
                  g->mixtab_ok ? g->mixtab : nullptr,
@@ -2676,6 +2897,7 @@ extern "C" int rl_gridop_mvm_top(rl_gridop* g, int q, const double* X, double* Y
                                  void* stream) {
     if (!g) return fail(RL_EINVAL, "gridop is NULL");
     if (q < 0 || q >= g->Q) return fail(RL_EINVAL, "rl_gridop_mvm_top: q out of range");
+    if (g->lead) return lead_mvm(g, q, X, Y, nvec, (hipStream_t)stream);
     if (g->wide) {
         if (nvec < 0) return fail(RL_EINVAL, "nvec < 0");
         return rl_gridop_mvm_top(g->child, q, X, Y, nvec * g->D, stream);
@@ -2688,6 +2910,9 @@ extern "C" int rl_gridop_mvm_top(rl_gridop* g, int q, const double* X, double* Y
 extern "C" int rl_gridop_spectrum_host(rl_gridop* g, int q, double* out) {
     if (!g || !out) return fail(RL_EINVAL, "NULL argument");
     if (g->wide) return rl_gridop_spectrum_host(g->child, q, out);
+    if (g->lead)
+        return fail(RL_ELIMIT, "rl_gridop_spectrum_host: a 3-D grid keeps one 2-D spectrum per leading "
+                               "frequency, not one spectrum");
     if (q < 0 || q >= g->Q) return fail(RL_EINVAL, "rl_gridop_spectrum_host: q out of range");
     RL_HIP(hipSetDevice(g->device));
     std::vector<double> scr(g->L);
@@ -2710,6 +2935,7 @@ extern "C" int rl_gridop_spectrum_host(rl_gridop* g, int q, double* out) {
 // verification and buffers of the structured forms, intermediates of the transform kernels
 // (second set for the two-stream chunks); a wide operator: its row buffer and its child
 int gridop_prepare(rl_gridop* g, int nvec) {
+    if (g->lead) return lead_reserve(g, nvec);
     if (g->wide) {
         RL_TRY(wide_reserve(g, nvec));
         return gridop_prepare(g->child, nvec * g->D);
@@ -2727,6 +2953,7 @@ extern "C" int rl_gridop_set_rank_hint(rl_gridop* g, int rank) {
     if (rank != 0 && rank != 24 && rank != 32 && rank != 36 && rank != 40 && rank != 48)
         return fail(RL_EINVAL, "rl_gridop_set_rank_hint: rank must be 0 or one of 24, 32, 36, 40, 48");
     if (g->wide) return rl_gridop_set_rank_hint(g->child, rank);
+    if (g->lead) return RL_OK;      // 3-D grid: no polynomial form to hint
     g->lr_rank_hint = rank;
     return RL_OK;
 }
@@ -2735,7 +2962,7 @@ extern "C" int rl_gridop_project(rl_gridop* g, const double* X, int nvec, int ra
                                  void* stream) {
     if (!g || !X || !out) return fail(RL_EINVAL, "rl_gridop_project: NULL argument");
     if (nvec < 0) return fail(RL_EINVAL, "rl_gridop_project: nvec < 0");
-    if (g->wide || !g->lr_try) return fail(RL_ELIMIT, "rl_gridop_project: this grid has no polynomial basis (1-D grids of >= 96 points, D <= 16)");
+    if (g->wide || g->lead || !g->lr_try) return fail(RL_ELIMIT, "rl_gridop_project: this grid has no polynomial basis (1-D grids of >= 96 points, D <= 16)");
     if (rank != 24 && rank != 32 && rank != 36 && rank != 40 && rank != 48)
         return fail(RL_EINVAL, "rl_gridop_project: rank must be one of 24, 32, 36, 40, 48");
     if (nvec == 0) return RL_OK;
@@ -2765,7 +2992,7 @@ extern "C" int rl_gridop_poly_coeffs(rl_gridop* g, int q, double* out, int cap, 
     if (!g || !rank) return fail(RL_EINVAL, "rl_gridop_poly_coeffs: NULL argument");
     if (q < 0 || q >= g->Q) return fail(RL_EINVAL, "rl_gridop_poly_coeffs: q out of range");
     *rank = 0;
-    if (g->wide || !g->lr_try) return RL_OK;
+    if (g->wide || g->lead || !g->lr_try) return RL_OK;
     RL_HIP(hipSetDevice(g->device));
     RL_TRY(lr_ensure(g));
     if (q >= (int)g->top_form.size() || g->top_form[q] != 1) return RL_OK;

@@ -174,6 +174,17 @@ struct rl_gridop {
     double* wide_B = nullptr;   // [max_tops][D][D]
     double* wide_Z = nullptr;   // T_q X of one top: nvec * D * m
     size_t wide_Z_cap = 0;
+    // 3-D grid m0 x m1 x m2 (rl_lead.h): a real transform along the leading axis (k_lead_fwd),
+    // one 2-D product over (m1, m2) per leading frequency f < F = N0 / 2 + 1 -- kids[f], a
+    // complete 2-D operator with D outputs holding the real rows sum_j c_q[j] cos(2 pi f j / N0)
+    // and the caller's couplings, applied to the real and the imaginary slab as two vectors --
+    // and the inverse transform (k_lead_inv).  One stream, in order.  No structured forms.
+    bool lead = false;
+    int m0 = 0, N0 = 0;
+    std::vector<rl_gridop*> kids;
+    double* lead_tw = nullptr;  // dev [N0 / 2][2]: exp(-2 pi i k / N0)
+    double *lead_x = nullptr, *lead_y = nullptr;   // [F][2][nvec][D][m1 m2] each
+    size_t lead_cap = 0;        // vectors they hold
     bool defer_expand = false;  // ski_mvm_int: leave the expansion to the W kernel (k_spmv_w_poly) ...
     bool expand_deferred = false;   // ... done: lr_zhat holds the mixed coefficients of the batch
     int lr_rejects = 0;         // consecutive parameter sets with a top the verification rejected

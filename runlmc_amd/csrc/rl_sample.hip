@@ -218,6 +218,11 @@ extern "C" int rl_sampler_destroy(rl_sampler* h) {
 
 extern "C" int rl_sampler_create(rl_gridop* g, rl_sampler** out) {
     if (!g || !out) return fail(RL_EINVAL, "rl_sampler_create: NULL argument");
+    if (g->lead) {
+        *out = nullptr;
+        return fail(RL_ELIMIT, "rl_sampler_create: no function draws on a 3-D grid (one- and "
+                               "two-dimensional grids only)");
+    }
     rl_sampler* h = new rl_sampler();
     h->g = g;
     h->device = g->device;

@@ -513,7 +513,7 @@ static int ski_w_poly(rl_ski* s, double* Yp, int nvec, const double* diag, const
 // structured W on a 1-D grid, every top row in the polynomial form, a large system)
 bool rp_ok(const rl_ski* s, int nvec) {
     const rl_gridop* g = s->g;
-    return s->extra.empty() && s->W4_base != nullptr && !s->h_base.empty() && !g->wide &&
+    return s->extra.empty() && s->W4_base != nullptr && !s->h_base.empty() && !g->wide && !g->lead &&
            g->lr_try && !g->lr_dirty && g->lr_ok && s->ngrid == g->D * g->m &&
            s->n < (1 << 28) &&          // (k_rp_expand's row accesses carry 32-bit byte offsets)
            // (the batch gate of the structured forms also gates this one: rl_gridop_set_form_gate
@@ -714,7 +714,7 @@ int ski_mvm_int(rl_ski* s, const double* Xp, double* Yp, int nvec, hipStream_t s
     const double* diag = s->has_noise && noise ? s->noise_diag : nullptr;
     // (a pending form decision is taken here, so that the path does not depend on whether an
     // earlier product happened to trigger it)
-    if (s->extra.empty() && !s->g->wide && !stream_capturing(st)) RL_TRY(lr_prepare(s->g, nvec));
+    if (s->extra.empty() && !s->g->wide && !s->g->lead && !stream_capturing(st)) RL_TRY(lr_prepare(s->g, nvec));
     // every top row in the polynomial form, a large system: F M F^T, no interpolation
     // products, no grid vector (rl_rowpoly.h).  (Buffers: the solver prepares them before it
     // captures; a plain product outside a capture prepares them here.)
@@ -832,7 +832,7 @@ extern "C" int rl_ski_mvm(rl_ski* s, const double* X, double* Y, int nvec, void*
     // row permutation of the batch (they were half of this product's time at C5).  The rows of
     // an output are contiguous in both orders, so runs, output borders and the noise array
     // (constant per output) serve both.
-    if (s->extra.empty() && !s->g->wide && !stream_capturing(st) && caller_order_same(s)) {
+    if (s->extra.empty() && !s->g->wide && !s->g->lead && !stream_capturing(st) && caller_order_same(s)) {
         RL_TRY(lr_prepare(s->g, nvec));
         if (rp_ok(s, nvec)) {
             RL_TRY(rp_prepare(s, nvec));

@@ -411,7 +411,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
         // points: a row of 30 entries, as on the weather workload, is a serial chain
         // of gathers inside the transform kernel: 1.45 vs 1.23 s per fit)
         const bool short_rows = (size_t)s->nnzWT <= (size_t)8 * s->ngrid;
-        const bool fuse_wt = fuse_w && short_rows && s->g->Q >= 1 && !s->g->wide &&
+        const bool fuse_wt = fuse_w && short_rows && s->g->Q >= 1 && !s->g->wide && !s->g->lead &&
                              ((size_t)nrhs + 1) / 2 <= s->g->chunk_pairs &&
                              !s->kn.no_fuse_wt;
         mb.fuse_wt = fuse_wt ? 1 : 0;
@@ -1407,6 +1407,7 @@ static int dz_available(rl_ski* s, bool* ok, const char** why) {
     rl_gridop* g = s->g;
     *ok = false;
     *why = "";
+    if (g->lead) { *why = "3-D grid: no polynomial form and no factorisation on a three-dimensional grid"; return RL_OK; }
     if (!s->extra.empty()) { *why = "kernels on several grids"; return RL_OK; }
     if (g->wide) {
         *why = g->D > RL_MAX_D ? "more than 16 outputs"

@@ -117,9 +117,9 @@ class GridKernel(Matrix):
         fk = functional_kernel
         # (a kern.Lags -- the distances with the grid's per-axis lags -- passes as it is)
         grid_dists = _distances(grid_dists)
-        if grid_dists.ndim > 2:
+        if grid_dists.ndim > 3:
             raise NotImplementedError(
-                'device GridKernel supports 1-D and 2-D grids')
+                'device GridKernel supports 1-D, 2-D and 3-D grids')
         kidx = fk.active_dims[active_dim]
         tops = as_f64(fk.eval_kernels_fixed_dim(grid_dists, active_dim)
                       ).reshape(len(kidx), -1)

@@ -105,10 +105,15 @@ class InterpolatedLLGP:
         self.loo_stats = None
         self._functional_kernel = functional_kernel
         self._functional_kernel.set_input_dim(self.input_dim)
-        if any(len(ad) > 2 for ad in functional_kernel.active_dims):
+        if any(len(ad) > 3 for ad in functional_kernel.active_dims):
             raise NotImplementedError(
-                'kernels may act on one or two input dimensions each (a Separable kernel over '
-                'three is usable through ExactLMCLikelihood only)')
+                'kernels may act on at most three input dimensions each')
+        if any(len(ad) == 3 for ad in functional_kernel.active_dims) and m is None:
+            # (the default grid has as many points PER AXIS as an output has data: n^3 points)
+            raise NotImplementedError(
+                'a kernel over three input dimensions needs the grid sizes: the default grid '
+                'would hold n points per axis, n^3 in all -- pass m=[m0, m1, m2] (shortest '
+                'axis first, at most 60 there), or use ExactLMCLikelihood for small data')
         self.y = np.hstack(self.Ys)
         self.kernel = None
         self.dists, self.interpolants, self.grid_axes = {}, {}, {}
