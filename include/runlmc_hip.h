@@ -47,7 +47,8 @@ typedef struct rl_exact rl_exact;
  * rl_diag_accumulate and rl_loo_reduce, leave-one-out cross-validation; callers
  * built against an older version must be rebuilt; rl_exact_set_factors joined version 8
  * without a bump: no declared signature changed, and so did rl_gridop_create_3d and
- * rl_gridop_info_3d, the three-dimensional grids).  A binding
+ * rl_gridop_info_3d, the three-dimensional grids, and rl_ski_set_pivchol, rl_ski_pivchol_info,
+ * rl_ski_pivchol_factor and rl_ski_pivchol_build_ms, the pivoted-Cholesky preconditioner).  A binding
  * compares rl_abi_version() with the RL_ABI_VERSION it was written against before its
  * first call (runlmc_amd/_lib.py does) instead of finding out through shifted arguments. */
 #define RL_ABI_VERSION 8
@@ -618,6 +619,44 @@ int rl_diag_accumulate(const double* Z, const double* X, const double* C, int nv
 int rl_loo_reduce(const double* y, const double* alpha, const double* dinv, const double* logscale,
                   long long n, double* mean, double* var, double* logp_partials, int* nblk,
                   void* stream);
+
+/* ---- Pivoted-Cholesky preconditioner (csrc/rl_pivchol.h; no reference twin) ------------------
+ * rl_ski_factor reports *available = 0 for every operator without the polynomial form: 2-D and 3-D
+ * grids, kernels on several grids, D > 16, rows whose spectrum the polynomial subspace does not
+ * hold.  The standard preconditioner of such operators needs their product and their diagonal only:
+ *     P = L L^T + E,   L (n x k) the rank-k pivoted (greedy, largest residual diagonal first)
+ *     Cholesky factor of the kernel part  sum_t W_t K_t W_t^T,   E = diag(eps),
+ *     P^-1 r = E^-1 r - E^-1 L G^-1 L^T E^-1 r,   G = I + L^T E^-1 L  (k x k, host Cholesky G = C C^T),
+ *     log det P = sum_i log eps_i + 2 sum_j log C_jj.
+ * Opt-in per handle, nothing changes without it:
+ * rl_ski_set_pivchol: rank 0 .. 256 (RL_EINVAL beyond), 0 = off (the default), clipped to n at the
+ *   build; rel_tol in [0, 1): a step whose pivot d_p <= rel_tol max_i d_i^(0) ends the factor (zero
+ *   columns from there on; 1e-10 is the usual value: the residual is then roundoff of the product).
+ * With a rank set, rl_ski_factor still prefers the polynomial factorisation (*available 1, 2, 3 as
+ * before, bit for bit); only where it would report 0 it builds P and reports *available = 4,
+ * *logdet = 0 (P is not K~; rl_ski_precond_sample gives log det P), *cond = the squared pivot ratio
+ * of chol(G).  The build runs once per parameter / noise update (k single-vector products, no host
+ * synchronisation between them; every sum in a fixed order: two builds of one operator give the
+ * same bits) and is cached on the handle.  The only condition on the noise: positive (it need not
+ * be constant per output).  Zero noise: *available = 0 with the reason.
+ * In mode 4 rl_solve_pcg, rl_solve_pcg_lanczos, rl_ski_precond_apply and rl_ski_precond_sample work
+ * as in modes 2 and 3 (the sample map is S = E^1/2 + L Ms L^T E^-1/2 with S S^T = P: when the Gram
+ * matrix L^T E^-1 L is numerically singular the trailing columns of L are dropped until its Cholesky
+ * holds, and the reduced rank is reported); rl_solve_direct, rl_ski_project and
+ * rl_ski_inverse_diag answer RL_ELIMIT and name the pivoted-Cholesky preconditioner.
+ * Test readouts (RL_ELIMIT unless the handle is in mode 4; any pointer may be NULL):
+ * rl_ski_pivchol_info: *rank_used = columns in use; pivots host [min(rank, n)]: the pivot rows in
+ *   the caller's numbering; pivot_values host [min(rank, n)]: the residual diagonal at each pivot
+ *   when it was chosen; resid_diag_dev dev [n], caller's row order: the residual diagonal after
+ *   the last step.
+ * rl_ski_pivchol_factor: L_dev dev [rank_used][n], caller's row order: the factor's columns.
+ * rl_ski_pivchol_build_ms: host out3 = milliseconds of the last build on the host's clock:
+ *   diagonal; the k products with their step kernels; Gram matrix and host maps.               */
+int rl_ski_set_pivchol(rl_ski* s, int rank, double rel_tol);
+int rl_ski_pivchol_info(rl_ski* s, int* rank_used, int* pivots, double* pivot_values,
+                        double* resid_diag_dev);
+int rl_ski_pivchol_factor(rl_ski* s, double* L_dev);
+int rl_ski_pivchol_build_ms(rl_ski* s, double* out3);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,10 @@ _SIGNATURES = {
     'rl_pathwise_residual': [_vp, _vp, _vp, _vp, _vp, _i, ctypes.c_longlong, _vp],
     'rl_ski_inverse_diag': [_vp, _vp, _c_int_p, _vp],
     'rl_ski_precond_apply': [_vp, _vp, _vp, _i, _vp],
+    'rl_ski_set_pivchol': [_vp, _i, _d],
+    'rl_ski_pivchol_info': [_vp, _c_int_p, _vp, _vp, _vp],
+    'rl_ski_pivchol_factor': [_vp, _vp],
+    'rl_ski_pivchol_build_ms': [_vp, _vp],
     'rl_diag_accumulate': [_vp, _vp, _vp, _i, ctypes.c_longlong, _vp, _vp, _vp],
     'rl_loo_reduce': [_vp, _vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _c_int_p, _vp],
 }

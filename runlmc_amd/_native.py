@@ -290,9 +290,44 @@ class SkiOp:
         self.factor_reason = ('' if av.value else
                               self.lib.cdll.rl_last_error().decode())
         # 1: the factorisation is K~^-1 (every top row in the polynomial form); 2: it inverts the
-        # operator's projection on the polynomial subspace -- a preconditioner (solve_pcg)
+        # operator's projection on the polynomial subspace -- a preconditioner (solve_pcg); 3: the
+        # same on the handle's larger basis (up to 192 polynomials per output); 4: the
+        # pivoted-Cholesky preconditioner of set_pivchol, where the operator has none of those
         self.factor_mode = int(av.value)
         return bool(av.value), float(ld.value), float(cond.value)
+
+    def set_pivchol(self, rank, rel_tol=1e-10):
+        """Opt in to the pivoted-Cholesky preconditioner P = L L^T + diag(eps) of the given rank
+        (0 .. 256; 0 switches it off) for operators without a polynomial factorisation
+        (rl_ski_set_pivchol).  ValueError for a rank that is not an int in that range."""
+        if isinstance(rank, bool) or not isinstance(rank, (int, np.integer)):
+            raise ValueError('rank must be an int in 0 .. 256, got %r' % (rank,))
+        if not 0 <= int(rank) <= 256:
+            raise ValueError('rank must be an int in 0 .. 256, got %r' % (rank,))
+        self.lib.call('rl_ski_set_pivchol', self._h, int(rank), float(rel_tol))
+        self.pivchol_rank = int(rank)
+
+    def pivchol_info(self):
+        """(rank_used, pivots, pivot_values, resid_diag): the state of the pivoted-Cholesky build
+        (rl_ski_pivchol_info): pivot rows in the caller's numbering and the residual diagonal at
+        each when it was chosen (numpy, one per requested step), the residual diagonal after the
+        last step (device tensor (n,), caller's row order)."""
+        k = min(int(getattr(self, 'pivchol_rank', 0)), self.n)
+        used = ctypes.c_int()
+        piv = np.zeros(max(k, 1), dtype=np.int32)
+        val = np.zeros(max(k, 1))
+        resid = torch.empty((self.n,), dtype=torch.float64, device=self.device)
+        self.lib.call('rl_ski_pivchol_info', self._h, ctypes.byref(used), host_ptr(piv),
+                      host_ptr(val), dev_ptr(resid))
+        return int(used.value), piv[:k], val[:k], resid
+
+    def pivchol_factor(self):
+        """L^T as a (rank_used, n) device tensor in the caller's row order: row j is column j of
+        the pivoted-Cholesky factor (rl_ski_pivchol_factor)."""
+        used = self.pivchol_info()[0]
+        out = torch.empty((used, self.n), dtype=torch.float64, device=self.device)
+        self.lib.call('rl_ski_pivchol_factor', self._h, dev_ptr(out))
+        return out
 
     def project(self, X):
         """(k, D, r) tensor of Phi^T W^T x per output on the orthonormal polynomials of the

@@ -46,6 +46,9 @@ def _indices(indices, n):
 def _why_not_direct(ski):
     if ski.factor_mode == 0:
         return ski.factor_reason
+    if ski.factor_mode == 4:
+        return ('the factorisation of this operator is the pivoted-Cholesky preconditioner '
+                '(rl_ski_factor: available = 4), not K~^-1: it has no inverse diagonal')
     return ('the factorisation of this operator is a preconditioner, not K~^-1 (rl_ski_factor: '
             'available = %d): not every top row is in the polynomial form' % ski.factor_mode)
 

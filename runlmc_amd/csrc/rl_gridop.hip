@@ -919,6 +919,12 @@ static int set_commit(rl_gridop* g, int Q, const double* tops, const std::vector
     return rc;
 }
 
+// (the bodies of rl_gridop_set_lmc / rl_gridop_set_dense: the handles a wide or a 3-D operator
+// owns are set through these, without the host copies the entry points keep)
+static int set_lmc_impl(rl_gridop* g, int Q, const double* tops, const int* ranks,
+                        const double* coreg_vecs, const double* coreg_diags);
+static int set_dense_impl(rl_gridop* g, int Q, const double* tops, const double* B);
+
 // wide operator (D > RL_MAX_D): the child takes the top rows alone, the parent keeps the
 // dense couplings B_q.  A failure leaves the handle without parameters.
 static int wide_set(rl_gridop* g, int Q, const double* tops, const std::vector<double>& B) {
@@ -926,7 +932,7 @@ static int wide_set(rl_gridop* g, int Q, const double* tops, const std::vector<d
     g->Q = 0;
     std::vector<int> zero(Q, 0);
     std::vector<double> ones(Q, 1.0);
-    RL_TRY(rl_gridop_set_lmc(g->child, Q, tops, zero.data(), nullptr, ones.data()));
+    RL_TRY(set_lmc_impl(g->child, Q, tops, zero.data(), nullptr, ones.data()));
     RL_HIP(hipMemcpy(g->wide_B, B.data(), B.size() * sizeof(double), hipMemcpyHostToDevice));
     g->Q = Q;
     return RL_OK;
@@ -973,14 +979,14 @@ static int lead_set(rl_gridop* g, int Q, const double* tops,
     return RL_OK;
 }
 
-extern "C" int rl_gridop_set_lmc(rl_gridop* g, int Q, const double* tops, const int* ranks,
+static int set_lmc_impl(rl_gridop* g, int Q, const double* tops, const int* ranks,
                                  const double* coreg_vecs, const double* coreg_diags) {
     RL_TRY(set_check(g, Q, tops));
     if (!ranks || !coreg_diags) return fail(RL_EINVAL, "rl_gridop_set_lmc: NULL argument");
     const int D = g->D;
     if (g->lead)
         return lead_set(g, Q, tops, [&](rl_gridop* k, const double* rows) {
-            return rl_gridop_set_lmc(k, Q, rows, ranks, coreg_vecs, coreg_diags);
+            return set_lmc_impl(k, Q, rows, ranks, coreg_vecs, coreg_diags);
         });
     if (g->wide) {
         std::vector<double> B((size_t)Q * D * D, 0.0);
@@ -1022,7 +1028,7 @@ extern "C" int rl_gridop_set_lmc(rl_gridop* g, int Q, const double* tops, const 
             for (int i = 0; i < D; ++i)
                 B[((size_t)q * D + i) * D + i] += coreg_diags[(size_t)q * D + i];
         }
-        return rl_gridop_set_dense(g, Q, tops, B.data());
+        return set_dense_impl(g, Q, tops, B.data());
     }
     for (int q = 0; q < Q; ++q) {
         if (ranks[q] > 0 && !coreg_vecs)
@@ -1077,13 +1083,13 @@ static void jacobi_eig(std::vector<double>& a, int n, std::vector<double>& w,
     for (int i = 0; i < n; ++i) w[i] = a[(size_t)i * n + i];
 }
 
-extern "C" int rl_gridop_set_dense(rl_gridop* g, int Q, const double* tops, const double* B) {
+static int set_dense_impl(rl_gridop* g, int Q, const double* tops, const double* B) {
     RL_TRY(set_check(g, Q, tops));
     if (!B) return fail(RL_EINVAL, "rl_gridop_set_dense: B is NULL");
     const int D = g->D;
     if (g->lead)
         return lead_set(g, Q, tops, [&](rl_gridop* k, const double* rows) {
-            return rl_gridop_set_dense(k, Q, rows, B);
+            return set_dense_impl(k, Q, rows, B);
         });
     if (g->wide) {
         for (int q = 0; q < Q; ++q)
@@ -1120,6 +1126,38 @@ extern "C" int rl_gridop_set_dense(rl_gridop* g, int Q, const double* tops, cons
         }
     }
     return set_commit(g, Q, tops, A, W, Qi, kap);
+}
+
+// The entry points keep, for every kind of grid (1-D, 2-D, wide, 3-D), the host copies a caller of
+// the operator's DIAGONAL needs (rl_pivchol.h: k_pc_diag): the top rows and the dense couplings.
+static void keep_host_params(rl_gridop* g, int Q, const double* tops, std::vector<double>&& B) {
+    // (set_commit has copied the rows already where a structured form may want them)
+    if (g->lead || g->wide || !(g->lr_try || g->sf_try)) g->h_tops.assign(tops, tops + (size_t)Q * g->m);
+    g->pc_hB = std::move(B);
+    ++g->pc_ver;
+}
+
+extern "C" int rl_gridop_set_lmc(rl_gridop* g, int Q, const double* tops, const int* ranks,
+                                 const double* coreg_vecs, const double* coreg_diags) {
+    RL_TRY(set_lmc_impl(g, Q, tops, ranks, coreg_vecs, coreg_diags));
+    const int D = g->D;
+    std::vector<double> B((size_t)Q * D * D, 0.0);
+    size_t row = 0;
+    for (int q = 0; q < Q; ++q) {
+        for (int r = 0; r < ranks[q]; ++r, ++row)
+            for (int i = 0; i < D; ++i)
+                for (int j = 0; j < D; ++j)
+                    B[((size_t)q * D + i) * D + j] += coreg_vecs[row * D + i] * coreg_vecs[row * D + j];
+        for (int i = 0; i < D; ++i) B[((size_t)q * D + i) * D + i] += coreg_diags[(size_t)q * D + i];
+    }
+    keep_host_params(g, Q, tops, std::move(B));
+    return RL_OK;
+}
+
+extern "C" int rl_gridop_set_dense(rl_gridop* g, int Q, const double* tops, const double* B) {
+    RL_TRY(set_dense_impl(g, Q, tops, B));
+    keep_host_params(g, Q, tops, std::vector<double>(B, B + (size_t)Q * g->D * g->D));
+    return RL_OK;
 }
 
 template <int D>

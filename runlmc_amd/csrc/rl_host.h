@@ -231,7 +231,10 @@ struct rl_gridop {
     int lr_np = 0;              // polynomial tops among the Q
     // per-top forms (decided by forms_setup at every parameter update):
     //   0 transform kernels, 1 polynomial-subspace form, 2 recursive filter (rl_filter.h)
-    std::vector<double> h_tops;     // host copy of the top rows [Q][m]
+    std::vector<double> h_tops;     // host copy of the top rows [Q][m] (every grid, every set_* path)
+    std::vector<double> pc_hB;      // host [Q][D][D]: the dense couplings of the current parameters (every grid;
+                                    // the pivoted-Cholesky preconditioner's diagonal, rl_pivchol.h)
+    unsigned long long pc_ver = 0;  // bumped with them (param_ver does not move on a wide handle)
     std::vector<int> top_form;
     bool st_ok = false;         // every top is 1 or 2 and at least one is 2: the operator runs as
                                 // polynomial part + filter part, nothing through the transforms
@@ -326,6 +329,44 @@ struct SkiTerm {
     int wt_xmax = 0, wt_emax = 0;
     int w_xmax = 0;            // largest grid range of RL_THREADS consecutive data rows
     std::vector<int> h_base;   // host copy of W4_base (row blocks per output, polynomial rounds)
+};
+
+// Pivoted-Cholesky preconditioner P = L L^T + E of a handle (rl_pivchol.h; rl_solve.hip pc_*):
+// opt-in (rank > 0), built where the polynomial factorisation is not available, cached by the
+// parameter versions of ALL the handle's grids and the noise version, internal row order.
+struct PcState {
+    int rank = 0;                       // requested (0: off)
+    double rel_tol = 1e-10;
+    bool valid = false;                 // built for the versions below
+    bool active = false;                // the factorisation the last dz_ensure settled on is this one (mode 4)
+    unsigned long long param_sum = 0, noise_ver = 0;
+    int k = 0, kp = 0;                  // rank clipped to n; rounded up to 16 (rows of L)
+    int rank_used = 0;                  // columns before the first zero column (less what the sample map dropped)
+    double logdet = 0.0, cond = 0.0;    // log det P; squared pivot ratio of chol(G)
+    std::vector<int> h_piv;             // host [k]
+    std::vector<double> h_pivval;       // host [k]
+    double* L = nullptr;                // dev [kp][n]
+    size_t L_cap = 0;
+    double *d = nullptr, *row = nullptr, *e = nullptr;   // dev [n]: residual diagonal, K e_p, one-hot vector
+    int* mark = nullptr;                // dev [n]: 1 on rows that were pivots
+    int* piv = nullptr;                 // dev [RL_PC_MAXRANK]
+    double* pivval = nullptr;           // dev [RL_PC_MAXRANK + 1]: d at the pivots, then max d^(0)
+    double* pv = nullptr;               // dev [RL_PC_NBLK]: arg-max partials
+    int* pi = nullptr;
+    double *inv = nullptr, *isq = nullptr, *sq = nullptr;   // dev [n]: 1 / eps, 1 / sqrt(eps), sqrt(eps)
+    unsigned long long eps_ver = ~0ull;
+    double sum_log_eps = 0.0;
+    double *Mt = nullptr, *Mst = nullptr;   // dev [kp][kp]: -G^-1 and the sample map, transposed
+    bool sample_ok = false;
+    double* part = nullptr;             // dev [chunks][nvp][kp]: k_pc_project's partial sums
+    size_t part_cap = 0;
+    double* cT = nullptr;               // dev [kp][nvp]
+    size_t cT_cap = 0;
+    std::vector<double*> tops;          // dev, per term: top rows [Q][m] where the grid keeps none
+    std::vector<size_t> tops_cap;
+    std::vector<double*> B;             // dev, per term: couplings [Q][D][D]
+    std::vector<size_t> B_cap;
+    double build_ms[4] = {0, 0, 0, 0};  // last build: diagonal / products / step kernels / Gram + host
 };
 
 // buffers of one rl_solve_batch call
@@ -478,6 +519,7 @@ struct rl_ski {
     double* dz_part = nullptr;          // dev [cap][RL_DZ_NBLK] partial sums, then [cap] norms
     int* dz_go = nullptr;               // dev [cap]: systems still being refined
     size_t dz_rhs_cap = 0;
+    PcState pc;                         // the pivoted-Cholesky preconditioner (rl_ski_set_pivchol)
 };
 
 // destroys a half-built handle on every early return of a create function

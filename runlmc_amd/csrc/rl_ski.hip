@@ -252,6 +252,17 @@ extern "C" int rl_ski_destroy(rl_ski* s) {
                     s->hz_F, s->hz_ones, s->hz_part, s->hz_zhat, s->hz_tmp, s->hz_S, s->hz_P, s->dz_Zh, s->dz_isq, s->dz_smp, s->dz_rec};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    {
+        PcState& pc = s->pc;
+        void* pcp[] = {pc.L, pc.d, pc.row, pc.e, pc.mark, pc.piv, pc.pivval, pc.pv, pc.pi, pc.inv, pc.isq,
+                       pc.sq, pc.Mt, pc.Mst, pc.part, pc.cT};
+        for (void* p : pcp)
+            if (p) (void)hipFree(p);
+        for (double* p : pc.tops)
+            if (p) (void)hipFree(p);
+        for (double* p : pc.B)
+            if (p) (void)hipFree(p);
+    }
     delete s;
     return RL_OK;
 }

@@ -5,6 +5,8 @@
 #include "rl_solver.h"
 #include "rl_direct.h"
 #include "rl_loo.h"
+#include "rl_pivchol.h"
+#include <chrono>
 
 void free_work(SolverWork& w) {
     for (double*& p : w.vec) { if (p) (void)hipFree(p); p = nullptr; }
@@ -1400,6 +1402,341 @@ static int hz_apply(rl_ski* s, const double* in, double* out, int nvec, hipStrea
     return RL_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Pivoted-Cholesky preconditioner (rl_pivchol.h): P = L L^T + E through Woodbury
+// ---------------------------------------------------------------------------
+static unsigned long long pc_param_sum(const rl_ski* s) {
+    // (versions only grow: the sum moves with every update of any of the handle's grids)
+    unsigned long long v = s->g->pc_ver;
+    for (const SkiTerm& t : s->extra) v += t.g->pc_ver;
+    return v;
+}
+static int pc_chunk_rows(int n) {
+    const int per = (n + RL_PC_CHUNKS - 1) / RL_PC_CHUNKS;
+    return std::max(256, (per + 3) / 4 * 4);
+}
+// partial sums and coefficients of nvec vectors
+static int pc_reserve(rl_ski* s, int nvec) {
+    PcState& pc = s->pc;
+    const int nvp = (nvec + 15) / 16 * 16;
+    const int nchunk = (s->n + pc_chunk_rows(s->n) - 1) / pc_chunk_rows(s->n);
+    const size_t need = (size_t)nchunk * nvp * pc.kp, needc = (size_t)pc.kp * nvp;
+    if (pc.part_cap < need) {
+        pc.part_cap = 0;
+        RL_TRY(hz_grow(&pc.part, need));
+        pc.part_cap = need;
+    }
+    if (pc.cT_cap < needc) {
+        pc.cT_cap = 0;
+        RL_TRY(hz_grow(&pc.cT, needc));
+        pc.cT_cap = needc;
+    }
+    return RL_OK;
+}
+// part[chunk][v][j] = sum_{i in chunk} L[j][i] sc_i X[v][i]  (buffers: pc_reserve)
+static void pc_project(rl_ski* s, const double* X, const double* sc, int nvec, hipStream_t st) {
+    PcState& pc = s->pc;
+    const int n = s->n, nvp = (nvec + 15) / 16 * 16, kp = pc.kp, rows = pc_chunk_rows(n);
+    const int nchunk = (n + rows - 1) / rows, nvt = nvp / 16;
+    const int JT = kp <= 64 ? 1 : kp <= 128 ? 2 : 4;
+    // (16 JT NVT accumulation registers a lane: at most 144)
+    const int NVT = nvt >= 9 && JT <= 2 ? 9 : nvt >= 4 ? 4 : nvt >= 2 ? 2 : 1;
+    const dim3 grid((nvt + NVT - 1) / NVT, nchunk);
+#define RL_PC_PROJ(NVT_, JT_)                                                                      \
+    if (NVT == NVT_ && JT == JT_)                                                                  \
+        RL_LAUNCH((k_pc_project<NVT_, JT_>), grid, dim3(256), 0, st, X, sc, (const double*)pc.L, n, \
+                  nvec, nvp, kp, rows, pc.part)
+    RL_PC_PROJ(1, 1); RL_PC_PROJ(2, 1); RL_PC_PROJ(4, 1); RL_PC_PROJ(9, 1);
+    RL_PC_PROJ(1, 2); RL_PC_PROJ(2, 2); RL_PC_PROJ(4, 2); RL_PC_PROJ(9, 2);
+    RL_PC_PROJ(1, 4); RL_PC_PROJ(2, 4); RL_PC_PROJ(4, 4);
+#undef RL_PC_PROJ
+}
+// out = a (.) in + b (.) L M L^T (sc (.) in), internal row order, in and out not aliased;
+// Mt: the map transposed, dev [kp][kp]; b NULL = 1
+static int pc_apply(rl_ski* s, const double* in, double* out, int nvec, hipStream_t st, const double* Mt,
+                    const double* sc, const double* a, const double* b) {
+    PcState& pc = s->pc;
+    const int n = s->n, nvp = (nvec + 15) / 16 * 16, kp = pc.kp, rows = pc_chunk_rows(n);
+    const int nchunk = (n + rows - 1) / rows, nvt = nvp / 16;
+    if (pc.part_cap < (size_t)nchunk * nvp * kp || pc.cT_cap < (size_t)kp * nvp)
+        return fail(RL_EINVAL, "internal: pivoted-Cholesky buffers not reserved");
+    pc_project(s, in, sc, nvec, st);
+    RL_LAUNCH(k_pc_map, dim3(nvp), dim3(256), (size_t)kp * sizeof(double), st, (const double*)pc.part,
+              nchunk, nvp, kp, Mt, pc.cT);
+    const int NVT = nvt >= 9 ? 9 : nvt >= 3 ? 3 : nvt >= 2 ? 2 : 1;
+    const dim3 grid((n + 127) / 128, (nvt + NVT - 1) / NVT);
+#define RL_PC_EXP(NVT_)                                                                            \
+    if (NVT == NVT_)                                                                               \
+        RL_LAUNCH((k_pc_expand<NVT_>), grid, dim3(256), 0, st, (const double*)pc.cT,               \
+                  (const double*)pc.L, n, nvec, nvp, kp, in, a, b, out)
+    RL_PC_EXP(1); RL_PC_EXP(2); RL_PC_EXP(3); RL_PC_EXP(9);
+#undef RL_PC_EXP
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+// one W K W^T term as k_pc_diag reads it; uploads what the grid keeps on the host only
+static int pc_term(rl_ski* s, int t, PcTerm* out) {
+    PcState& pc = s->pc;
+    rl_gridop* g = t == 0 ? s->g : s->extra[t - 1].g;
+    const int Q = g->Q, D = g->D, m = g->m;
+    if ((int)pc.tops.size() <= t) {
+        pc.tops.resize(t + 1, nullptr);
+        pc.tops_cap.resize(t + 1, 0);
+        pc.B.resize(t + 1, nullptr);
+        pc.B_cap.resize(t + 1, 0);
+    }
+    const size_t nt = (size_t)Q * m, nb = (size_t)Q * D * D;
+    const double* tops = g->tops;
+    if (g->lead || g->wide || tops == nullptr) {
+        if (pc.tops_cap[t] < nt) {
+            pc.tops_cap[t] = 0;
+            RL_TRY(hz_grow(&pc.tops[t], nt));
+            pc.tops_cap[t] = nt;
+        }
+        RL_HIP(hipMemcpy(pc.tops[t], g->h_tops.data(), nt * sizeof(double), hipMemcpyHostToDevice));
+        tops = pc.tops[t];
+    }
+    if (pc.B_cap[t] < nb) {
+        pc.B_cap[t] = 0;
+        RL_TRY(hz_grow(&pc.B[t], nb));
+        pc.B_cap[t] = nb;
+    }
+    RL_HIP(hipMemcpy(pc.B[t], g->pc_hB.data(), nb * sizeof(double), hipMemcpyHostToDevice));
+    out->tops = tops;
+    out->B = pc.B[t];
+    out->m = m;
+    out->Q = Q;
+    // (a 3-D handle's geo holds its inner sizes, m / (m1 m2) leading planes; 1-D: m1 == 0)
+    out->e1 = g->geo.m1 > 0 ? g->geo.m1 : 1;
+    out->e2 = g->geo.m1 > 0 ? g->geo.m2 : m;
+    if (t == 0) {
+        out->indptr = s->W_indptr; out->indices = s->W_indices; out->w = s->W_data;
+    } else {
+        const SkiTerm& e = s->extra[t - 1];
+        out->indptr = e.W_indptr; out->indices = e.W_indices; out->w = e.W_data;
+    }
+    return RL_OK;
+}
+
+// builds (or rebuilds) the preconditioner for the current parameters and noise; *ok = false
+// with a reason when there is none
+static int pc_ensure(rl_ski* s, bool* ok, const char** why) {
+    PcState& pc = s->pc;
+    rl_gridop* g = s->g;
+    *ok = false;
+    *why = "";
+    const int n = s->n;
+    const unsigned long long psum = pc_param_sum(s);
+    const int k = std::min(pc.rank, n), kp = (k + 15) / 16 * 16;
+    if (pc.valid && pc.param_sum == psum && pc.noise_ver == s->noise_ver && pc.k == k) {
+        *ok = true;
+        return RL_OK;
+    }
+    pc.valid = false;
+    const int nterm = 1 + (int)s->extra.size();
+    for (int t = 0; t < nterm; ++t) {
+        const rl_gridop* gt = t == 0 ? g : s->extra[t - 1].g;
+        if (gt->Q < 1 || gt->h_tops.size() < (size_t)gt->Q * gt->m ||
+            gt->pc_hB.size() < (size_t)gt->Q * gt->D * gt->D) {
+            *why = "pivoted-Cholesky preconditioner: no parameters set";
+            return RL_OK;
+        }
+    }
+    if (!s->has_noise || (int)s->h_noise.size() != n) { *why = "pivoted-Cholesky preconditioner: no noise set"; return RL_OK; }
+    for (int i = 0; i < n; ++i)
+        if (!(s->h_noise[i] > 0.0) || !std::isfinite(s->h_noise[i])) {
+            *why = "pivoted-Cholesky preconditioner: noise is not positive";
+            return RL_OK;
+        }
+    RL_HIP(hipSetDevice(g->device));
+    hipStream_t st = nullptr;
+    using clk = std::chrono::steady_clock;
+    const auto t_start = clk::now();
+    if (pc.eps_ver != s->noise_ver || pc.inv == nullptr) {
+        std::vector<double> v((size_t)n);
+        if (!pc.inv) {
+            RL_TRY(hz_grow(&pc.inv, (size_t)n));
+            RL_TRY(hz_grow(&pc.isq, (size_t)n));
+            RL_TRY(hz_grow(&pc.sq, (size_t)n));
+        }
+        for (int i = 0; i < n; ++i) v[i] = 1.0 / s->h_noise[i];
+        RL_HIP(hipMemcpy(pc.inv, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+        for (int i = 0; i < n; ++i) v[i] = 1.0 / std::sqrt(s->h_noise[i]);
+        RL_HIP(hipMemcpy(pc.isq, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+        for (int i = 0; i < n; ++i) v[i] = std::sqrt(s->h_noise[i]);
+        RL_HIP(hipMemcpy(pc.sq, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+        double sl = 0.0;
+        for (int i = 0; i < n; ++i) sl += std::log(s->h_noise[i]);
+        pc.sum_log_eps = sl;
+        pc.eps_ver = s->noise_ver;
+    }
+    if (pc.L_cap < (size_t)kp * n) {
+        pc.L_cap = 0;
+        RL_TRY(hz_grow(&pc.L, (size_t)kp * n));
+        pc.L_cap = (size_t)kp * n;
+    }
+    if (!pc.d) {
+        RL_TRY(hz_grow(&pc.d, (size_t)n));
+        RL_TRY(hz_grow(&pc.row, (size_t)n));
+        RL_TRY(hz_grow(&pc.e, (size_t)n));
+        RL_TRY(hz_grow(&pc.mark, (size_t)n));
+        RL_TRY(hz_grow(&pc.piv, (size_t)RL_PC_MAXRANK));
+        RL_TRY(hz_grow(&pc.pivval, (size_t)RL_PC_MAXRANK + 1));
+        RL_TRY(hz_grow(&pc.pv, (size_t)RL_PC_NBLK));
+        RL_TRY(hz_grow(&pc.pi, (size_t)RL_PC_NBLK));
+    }
+    pc.k = k;
+    pc.kp = kp;
+    if (pc.Mt) RL_HIP(hipFree(pc.Mt));
+    if (pc.Mst) RL_HIP(hipFree(pc.Mst));
+    pc.Mt = pc.Mst = nullptr;
+    RL_HIP(hipMalloc((void**)&pc.Mt, (size_t)kp * kp * sizeof(double)));
+    RL_HIP(hipMalloc((void**)&pc.Mst, (size_t)kp * kp * sizeof(double)));
+    // everything the single-vector products allocate lazily
+    RL_TRY(ski_reserve(s, 1));
+    RL_TRY(gridop_prepare(g, 1));
+    for (const SkiTerm& t : s->extra) RL_TRY(gridop_prepare(t.g, 1));
+    RL_HIP(hipMemsetAsync(pc.L, 0, (size_t)kp * n * sizeof(double), st));
+    RL_HIP(hipMemsetAsync(pc.e, 0, (size_t)n * sizeof(double), st));
+    RL_HIP(hipMemsetAsync(pc.mark, 0, (size_t)n * sizeof(int), st));
+    // 1. the diagonal, term by term
+    for (int t = 0; t < nterm; ++t) {
+        PcTerm pt;
+        RL_TRY(pc_term(s, t, &pt));
+        RL_LAUNCH(k_pc_diag, dim3((n + 255) / 256), dim3(256), 0, st, pt, n, g->D, t > 0 ? 1 : 0, pc.d);
+    }
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipStreamSynchronize(st));
+    const auto t_diag = clk::now();
+    // 2. k steps, no host synchronisation between them (the pivot stays on the device)
+    const int nb = std::max(1, std::min(RL_PC_NBLK, (n + 1023) / 1024));
+    const size_t red = 256 * (sizeof(double) + sizeof(int));
+    double* d0max = pc.pivval + RL_PC_MAXRANK;
+    RL_LAUNCH(k_pc_argmax, dim3(nb), dim3(256), red, st, (const double*)pc.d, n, pc.pv, pc.pi);
+    for (int j = 0; j < k; ++j) {
+        RL_LAUNCH(k_pc_pick, dim3(1), dim3(256), red, st, (const double*)pc.pv, (const int*)pc.pi, nb, j, n,
+                  pc.piv, pc.pivval, d0max, pc.e);
+        RL_TRY(ski_mvm_int(s, pc.e, pc.row, 1, st, nullptr, false));
+        RL_LAUNCH(k_pc_step, dim3(nb), dim3(256), RL_PC_MAXRANK * sizeof(double) + red, st, j,
+                  (const double*)pc.row, pc.L, n, (const int*)pc.piv, (const double*)pc.pivval,
+                  (const double*)d0max, pc.rel_tol, pc.d, pc.mark, pc.pv, pc.pi);
+    }
+    RL_HIP(hipGetLastError());
+    pc.h_piv.assign(k, 0);
+    pc.h_pivval.assign(k, 0.0);
+    double h_d0 = 0.0;
+    RL_HIP(hipMemcpyAsync(pc.h_piv.data(), pc.piv, (size_t)k * sizeof(int), hipMemcpyDeviceToHost, st));
+    RL_HIP(hipMemcpyAsync(pc.h_pivval.data(), pc.pivval, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
+    RL_HIP(hipMemcpyAsync(&h_d0, d0max, sizeof(double), hipMemcpyDeviceToHost, st));
+    RL_HIP(hipStreamSynchronize(st));
+    const auto t_steps = clk::now();
+    int r = k;
+    for (int j = 0; j < k; ++j)
+        if (!(pc.h_pivval[j] > pc.rel_tol * h_d0) || !(pc.h_pivval[j] > 0.0)) { r = j; break; }
+    if (r == 0) {
+        *why = "pivoted-Cholesky preconditioner: the kernel part of the operator has no positive diagonal entry";
+        return RL_OK;
+    }
+    // 3. H = L^T E^-1 L: the projection of L's own columns (a batch of kp vectors), chunks summed in order
+    RL_TRY(pc_reserve(s, kp));
+    pc_project(s, pc.L, pc.inv, kp, st);
+    {
+        const int rows = pc_chunk_rows(n), nchunk = (n + rows - 1) / rows;
+        const size_t total = (size_t)kp * kp;
+        RL_LAUNCH(k_pc_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)pc.part,
+                  nchunk, total, pc.cT);       // (cT holds kp * nvp >= kp * kp doubles here)
+    }
+    RL_HIP(hipGetLastError());
+    std::vector<double> H((size_t)kp * kp);
+    RL_HIP(hipMemcpyAsync(H.data(), pc.cT, H.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    RL_HIP(hipStreamSynchronize(st));
+    // host: symmetrised leading blocks; the sample map's Cholesky of H decides the rank that holds
+    auto lead = [&](int rr, double add) {
+        std::vector<double> a((size_t)rr * rr);
+        for (int i = 0; i < rr; ++i)
+            for (int j = 0; j < rr; ++j)
+                a[(size_t)i * rr + j] = 0.5 * (H[(size_t)i * kp + j] + H[(size_t)j * kp + i]) + (i == j ? add : 0.0);
+        return a;
+    };
+    auto lower = [](std::vector<double>& a, int rr) {
+        for (int i = 0; i < rr; ++i)
+            for (int j = i + 1; j < rr; ++j) a[(size_t)i * rr + j] = 0.0;
+    };
+    std::vector<double> Rl;                 // H = Rl Rl^T (lower)
+    for (; r > 0; --r) {
+        Rl = lead(r, 0.0);
+        if (dz_chol(Rl, r)) break;
+    }
+    if (r == 0) { *why = "pivoted-Cholesky preconditioner: the factor's Gram matrix is not positive definite"; return RL_OK; }
+    lower(Rl, r);
+    std::vector<double> C = lead(r, 1.0);   // G = I + H = C C^T
+    if (!dz_chol(C, r)) { *why = "pivoted-Cholesky preconditioner: I + L^T E^-1 L is not positive definite"; return RL_OK; }
+    lower(C, r);
+    double ld = 0.0, cmin = C[0], cmax = C[0];
+    for (int j = 0; j < r; ++j) {
+        const double c = C[(size_t)j * r + j];
+        ld += std::log(c);
+        cmin = std::min(cmin, c);
+        cmax = std::max(cmax, c);
+    }
+    std::vector<double> Ci, Ri;
+    dz_tri_inverse(C, r, Ci);
+    dz_tri_inverse(Rl, r, Ri);
+    // Mt = -(G^-1)^T = -Ci^T Ci (symmetric), padded with zeros to kp
+    std::vector<double> Mt((size_t)kp * kp, 0.0), Mst((size_t)kp * kp, 0.0);
+    for (int i = 0; i < r; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double sacc = 0.0;
+            for (int q = i; q < r; ++q) sacc += Ci[(size_t)q * r + i] * Ci[(size_t)q * r + j];
+            Mt[(size_t)i * kp + j] = Mt[(size_t)j * kp + i] = -sacc;
+        }
+    // sample map: with R = Rl^T,  I + R R^T = I + Rl^T Rl = C2 C2^T,  Ms = R^-1 (C2 - I) R^-T = Ri^T (C2 - I) Ri
+    std::vector<double> C2((size_t)r * r, 0.0);
+    for (int i = 0; i < r; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double sacc = i == j ? 1.0 : 0.0;
+            for (int q = i; q < r; ++q) sacc += Rl[(size_t)q * r + i] * Rl[(size_t)q * r + j];
+            C2[(size_t)i * r + j] = C2[(size_t)j * r + i] = sacc;
+        }
+    pc.sample_ok = dz_chol(C2, r);
+    if (pc.sample_ok) {
+        lower(C2, r);
+        for (int i = 0; i < r; ++i) C2[(size_t)i * r + i] -= 1.0;
+        std::vector<double> T((size_t)r * r, 0.0);       // T = (C2 - I) Ri (lower times lower)
+        for (int i = 0; i < r; ++i)
+            for (int j = 0; j <= i; ++j) {
+                double sacc = 0.0;
+                for (int q = j; q <= i; ++q) sacc += C2[(size_t)i * r + q] * Ri[(size_t)q * r + j];
+                T[(size_t)i * r + j] = sacc;
+            }
+        for (int i = 0; i < r; ++i)                      // Ms = Ri^T T;  Mst[j][i] = Ms[i][j]
+            for (int j = 0; j < r; ++j) {
+                double sacc = 0.0;
+                for (int q = std::max(i, j); q < r; ++q) sacc += Ri[(size_t)q * r + i] * T[(size_t)q * r + j];
+                Mst[(size_t)j * kp + i] = sacc;
+            }
+    }
+    for (double v : Mt)
+        if (!std::isfinite(v)) { *why = "pivoted-Cholesky preconditioner: the solve map is not finite"; return RL_OK; }
+    RL_HIP(hipMemcpy(pc.Mt, Mt.data(), Mt.size() * sizeof(double), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(pc.Mst, Mst.data(), Mst.size() * sizeof(double), hipMemcpyHostToDevice));
+    const auto t_end = clk::now();
+    auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    pc.build_ms[0] = ms(t_start, t_diag);
+    pc.build_ms[1] = ms(t_diag, t_steps);
+    pc.build_ms[2] = 0.0;
+    pc.build_ms[3] = ms(t_steps, t_end);
+    pc.rank_used = r;
+    pc.logdet = pc.sum_log_eps + 2.0 * ld;
+    pc.cond = (cmax / cmin) * (cmax / cmin);
+    pc.param_sum = psum;
+    pc.noise_ver = s->noise_ver;
+    pc.valid = true;
+    *ok = true;
+    return RL_OK;
+}
+
 // May this handle's operator be inverted through its polynomial form?  Runs the pending
 // verification of the forms (whatever the batch gate says: the decision is the operator's,
 // not a batch's).  `why` receives the reason when not.
@@ -1432,7 +1769,7 @@ static int dz_available(rl_ski* s, bool* ok, const char** why) {
 
 // builds (or rebuilds, after a parameter / noise update) the factorisation; *ok = false with
 // a reason when the operator has no such form or the factorisation breaks down
-static int dz_ensure(rl_ski* s, bool* ok, const char** why) {
+static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
     rl_gridop* g = s->g;
     RL_TRY(dz_available(s, ok, why));
     if (!*ok) { s->dz_valid = false; return RL_OK; }
@@ -1610,10 +1947,30 @@ static int dz_ensure(rl_ski* s, bool* ok, const char** why) {
     return RL_OK;
 }
 
+// The factorisation every solve asks for: the polynomial form's where the operator has one
+// (modes 1-3, unchanged whatever rl_ski_set_pivchol said); else, with a rank set, the
+// pivoted-Cholesky preconditioner (mode 4, s->pc.active; no back-off: its build does not fail
+// for reasons a later parameter set would mend).
+static int dz_ensure(rl_ski* s, bool* ok, const char** why) {
+    s->pc.active = false;
+    RL_TRY(dz_ensure_poly(s, ok, why));
+    if (*ok || s->pc.rank <= 0) return RL_OK;
+    bool pok = false;
+    const char* pwhy = "";
+    RL_TRY(pc_ensure(s, &pok, &pwhy));
+    if (!pok) { *why = pwhy; return RL_OK; }
+    s->pc.active = true;
+    s->dz_exact = false;
+    s->dz_hz = false;
+    *ok = true;
+    return RL_OK;
+}
+
 // out = K~^-1 in (to roundoff), both in internal row order; in and out may not alias
 static int dz_apply(rl_ski* s, const double* in, double* out, int nvec, hipStream_t st,
                     const double* map = nullptr, const double* diag = nullptr) {
     rl_gridop* g = s->g;
+    if (s->pc.active) return pc_apply(s, in, out, nvec, st, s->pc.Mt, s->pc.inv, s->pc.inv, s->pc.inv);
     if (s->dz_hz) return hz_apply(s, in, out, nvec, st, map, diag);
     if (map == nullptr) map = s->dz_Zt;
     if (diag == nullptr) diag = s->dz_inv;
@@ -1639,9 +1996,11 @@ extern "C" int rl_ski_factor(rl_ski* s, int* available, double* logdet, double* 
     // (2: the factorisation inverts the operator's projection on the polynomial subspace -- a
     // preconditioner for rl_solve_pcg; its log det is not the operator's)
     // (3: the same on the 96-function basis of an operator without a polynomial row, hz_* above)
-    if (available) *available = ok ? (s->dz_exact ? 1 : s->dz_hz ? 3 : 2) : 0;
-    if (logdet) *logdet = ok && s->dz_exact ? s->dz_logdet : 0.0;
-    if (cond) *cond = ok ? s->dz_cond : 0.0;
+    // (4: the pivoted-Cholesky preconditioner of rl_ski_set_pivchol, where there is none of the above)
+    const bool pc = ok && s->pc.active;
+    if (available) *available = ok ? (pc ? 4 : s->dz_exact ? 1 : s->dz_hz ? 3 : 2) : 0;
+    if (logdet) *logdet = ok && !pc && s->dz_exact ? s->dz_logdet : 0.0;
+    if (cond) *cond = ok ? (pc ? s->pc.cond : s->dz_cond) : 0.0;
     if (!ok) (void)fail(RL_OK, std::string("direct solve not available: ") + why);
     return RL_OK;
 }
@@ -1655,6 +2014,9 @@ extern "C" int rl_ski_project(rl_ski* s, const double* X, int nvec, double* out,
     const char* why = "";
     RL_TRY(dz_ensure(s, &ok, &why));
     if (!ok) return fail(RL_ELIMIT, std::string("rl_ski_project: not available for this operator: ") + why);
+    if (s->pc.active)
+        return fail(RL_ELIMIT, "rl_ski_project: the factorisation is the pivoted-Cholesky preconditioner, "
+                               "which has no polynomial coefficients");
     if (!s->dz_exact) return fail(RL_ELIMIT, "rl_ski_project: not every top row is in the polynomial form");
     if (rank) *rank = g->lr_r;
     if (nvec == 0) return RL_OK;
@@ -1691,6 +2053,9 @@ extern "C" int rl_solve_direct(rl_ski* s, const double* B, double* X, int nrhs, 
     const char* why = "";
     RL_TRY(dz_ensure(s, &ok, &why));
     if (!ok) return fail(RL_ELIMIT, std::string("rl_solve_direct: not available for this operator: ") + why);
+    if (s->pc.active)
+        return fail(RL_ELIMIT, "rl_solve_direct: the factorisation is the pivoted-Cholesky preconditioner, "
+                               "not an inverse (rl_solve_pcg)");
     if (!s->dz_exact)
         return fail(RL_ELIMIT, "rl_solve_direct: not every top row is in the polynomial form -- the "
                                "factorisation is a preconditioner here (rl_solve_pcg)");
@@ -1862,12 +2227,17 @@ static int pcg_core(rl_ski* s, const double* B, double* X, int nrhs, double tol,
             s->dz_rec_cap = need;
         }
     }
-    RL_TRY(rp_prepare(s, std::max(nrhs, R)));
+    // (mode 4 has none of the polynomial form's tables: a 3-D or wide handle could not build them)
+    const bool pcm = s->pc.active;
+    if (!pcm) RL_TRY(rp_prepare(s, std::max(nrhs, R)));
     RL_TRY(ski_reserve(s, nrhs));
     RL_TRY(gridop_prepare(g, nrhs));
+    if (pcm)
+        for (const SkiTerm& t : s->extra) RL_TRY(gridop_prepare(t.g, nrhs));
     if (rp_ok(s, nrhs)) RL_TRY(rp_prepare(s, nrhs));
     RL_TRY(ski_reserve_perm(s, nrhs));
-    if (s->dz_hz) RL_TRY(hz_reserve(s, nrhs));
+    if (pcm) RL_TRY(pc_reserve(s, nrhs));
+    else if (s->dz_hz) RL_TRY(hz_reserve(s, nrhs));
     const size_t ve = (size_t)nrhs * n;
     if (s->dz_vec_cap < ve) {
         if (s->dz_res) RL_HIP(hipFree(s->dz_res));
@@ -1922,7 +2292,9 @@ static int pcg_core(rl_ski* s, const double* B, double* X, int nrhs, double tol,
     double *r = s->dz_res, *z = s->dz_cor, *p = s->dz_p, *q = s->dz_q;
     std::vector<double> res((size_t)nrhs, 0.0);
     std::vector<int> go((size_t)nrhs, 1), its((size_t)nrhs, 0), stop((size_t)nrhs, 0);
-    if (s->dz_hz) trace_once("solve: conjugate gradients preconditioned by the Woodbury inverse on 96 polynomials per output (rl_solve_pcg)");
+    if (pcm) trace_once(("solve: conjugate gradients preconditioned by the pivoted Cholesky of rank " +
+                         std::to_string(s->pc.rank_used) + " (k_pc_project / k_pc_map / k_pc_expand; rl_solve_pcg)").c_str());
+    else if (s->dz_hz) trace_once("solve: conjugate gradients preconditioned by the Woodbury inverse on 96 polynomials per output (rl_solve_pcg)");
     else trace_once("solve: conjugate gradients preconditioned by the polynomial subspace's Woodbury inverse (rl_solve_pcg)");
     RL_HIP(hipMemsetAsync(Xi, 0, ve * sizeof(double), st));
     RL_HIP(hipMemcpyAsync(r, Bi, ve * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -2068,6 +2440,25 @@ extern "C" int rl_ski_precond_sample(rl_ski* s, const double* Win, double* Rout,
     }
     RL_TRY(dz_ensure(s, &ok, &why));
     if (!ok) return fail(RL_ELIMIT, std::string("rl_ski_precond_sample: no factorisation for this operator: ") + why);
+    if (s->pc.active) {
+        // S = E^1/2 + L Ms L^T E^-1/2  (S S^T = P): the apply's three launches with another map
+        if (!s->pc.sample_ok) return fail(RL_ELIMIT, "rl_ski_precond_sample: no square-root map of the pivoted-Cholesky preconditioner");
+        if (logdet_p) *logdet_p = s->pc.logdet;
+        if (nvec == 0) return RL_OK;
+        RL_TRY(ski_reserve_perm(s, nvec));
+        RL_TRY(pc_reserve(s, nvec));
+        const double* Wi = Win;
+        double* Ri = Rout;
+        if (s->permuted) {
+            permute_rows(s, Win, s->P1, nvec, 0, st);
+            Wi = s->P1;
+            Ri = s->P2;
+        }
+        RL_TRY(pc_apply(s, Wi, Ri, nvec, st, s->pc.Mst, s->pc.isq, s->pc.sq, nullptr));
+        if (s->permuted) permute_rows(s, Ri, Rout, nvec, 1, st);
+        RL_HIP(hipGetLastError());
+        return RL_OK;
+    }
     if (!s->dz_Zh_valid) return fail(RL_ELIMIT, "rl_ski_precond_sample: no square-root map");
     if (logdet_p) *logdet_p = s->dz_logdet;
     if (nvec == 0) return RL_OK;
@@ -2117,6 +2508,9 @@ extern "C" int rl_ski_inverse_diag(rl_ski* s, double* out, int* exact, void* str
     const char* why = "";
     RL_TRY(dz_ensure(s, &ok, &why));
     if (!ok) return fail(RL_ELIMIT, std::string("rl_ski_inverse_diag: no factorisation for this operator: ") + why);
+    if (s->pc.active)
+        return fail(RL_ELIMIT, "rl_ski_inverse_diag: the factorisation is the pivoted-Cholesky preconditioner: "
+                               "no diagonal from it");
     if (s->dz_hz)
         return fail(RL_ELIMIT, "rl_ski_inverse_diag: the factorisation is on the 96-function basis, whose map is "
                                "kept in blocks of 48 functions: no diagonal from it");
@@ -2150,10 +2544,15 @@ extern "C" int rl_ski_precond_apply(rl_ski* s, const double* B, double* X, int n
     if (nvec == 0) return RL_OK;
     RL_HIP(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)stream;
-    RL_TRY(rp_prepare(s, std::max(nvec, g->lr_r)));
-    RL_TRY(ski_reserve_perm(s, nvec));
-    if (s->dz_hz) RL_TRY(hz_reserve(s, nvec));
-    RL_TRY(lr_reserve(g, nvec));
+    if (s->pc.active) {
+        RL_TRY(ski_reserve_perm(s, nvec));
+        RL_TRY(pc_reserve(s, nvec));
+    } else {
+        RL_TRY(rp_prepare(s, std::max(nvec, g->lr_r)));
+        RL_TRY(ski_reserve_perm(s, nvec));
+        if (s->dz_hz) RL_TRY(hz_reserve(s, nvec));
+        RL_TRY(lr_reserve(g, nvec));
+    }
     const double* Bi = B;
     double* Xi = X;
     if (s->permuted) {
@@ -2164,6 +2563,78 @@ extern "C" int rl_ski_precond_apply(rl_ski* s, const double* B, double* X, int n
     RL_TRY(dz_apply(s, Bi, Xi, nvec, st));
     if (s->permuted) permute_rows(s, Xi, X, nvec, 1, st);
     RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Pivoted-Cholesky preconditioner: the switch and the test readouts
+// ---------------------------------------------------------------------------
+extern "C" int rl_ski_set_pivchol(rl_ski* s, int rank, double rel_tol) {
+    if (!s) return fail(RL_EINVAL, "rl_ski_set_pivchol: NULL handle");
+    if (rank < 0 || rank > RL_PC_MAXRANK) return fail(RL_EINVAL, "rl_ski_set_pivchol: rank outside 0 .. 256");
+    if (!(rel_tol >= 0.0) || !(rel_tol < 1.0)) return fail(RL_EINVAL, "rl_ski_set_pivchol: rel_tol outside [0, 1)");
+    if (rank != s->pc.rank || rel_tol != s->pc.rel_tol) s->pc.valid = false;
+    s->pc.rank = rank;
+    s->pc.rel_tol = rel_tol;
+    s->pc.active = false;
+    return RL_OK;
+}
+
+// the built preconditioner of the current parameters, or RL_ELIMIT with the reason
+static int pc_current(rl_ski* s, const char* who) {
+    if (s->pc.rank <= 0)
+        return fail(RL_ELIMIT, std::string(who) + ": no pivoted-Cholesky rank is set on this handle (rl_ski_set_pivchol)");
+    bool ok = false;
+    const char* why = "";
+    RL_TRY(dz_ensure(s, &ok, &why));
+    if (!ok) return fail(RL_ELIMIT, std::string(who) + ": no factorisation for this operator: " + why);
+    if (!s->pc.active)
+        return fail(RL_ELIMIT, std::string(who) + ": the handle's factorisation is not the pivoted-Cholesky "
+                               "preconditioner (no rank set, or the polynomial form took priority)");
+    return RL_OK;
+}
+
+extern "C" int rl_ski_pivchol_info(rl_ski* s, int* rank_used, int* pivots, double* pivot_values,
+                                   double* resid_diag_dev) {
+    if (!s) return fail(RL_EINVAL, "rl_ski_pivchol_info: NULL handle");
+    RL_TRY(pc_current(s, "rl_ski_pivchol_info"));
+    const PcState& pc = s->pc;
+    if (rank_used) *rank_used = pc.rank_used;
+    // (pivots in the CALLER's row numbering)
+    for (int j = 0; j < pc.k; ++j) {
+        if (pivots) pivots[j] = s->permuted ? s->h_perm[pc.h_piv[j]] : pc.h_piv[j];
+        if (pivot_values) pivot_values[j] = pc.h_pivval[j];
+    }
+    if (resid_diag_dev) {
+        RL_HIP(hipSetDevice(s->g->device));
+        RL_LAUNCH(k_pc_unpermute, dim3((s->n + 255) / 256, 1), dim3(256), 0, (hipStream_t) nullptr,
+                  (const double*)pc.d, s->permuted ? (const int*)s->perm : (const int*)nullptr, s->n,
+                  resid_diag_dev);
+        RL_HIP(hipGetLastError());
+        RL_HIP(hipDeviceSynchronize());
+    }
+    return RL_OK;
+}
+
+extern "C" int rl_ski_pivchol_factor(rl_ski* s, double* L_dev) {
+    if (!s || !L_dev) return fail(RL_EINVAL, "rl_ski_pivchol_factor: NULL argument");
+    RL_TRY(pc_current(s, "rl_ski_pivchol_factor"));
+    const PcState& pc = s->pc;
+    RL_HIP(hipSetDevice(s->g->device));
+    RL_LAUNCH(k_pc_unpermute, dim3((s->n + 255) / 256, pc.rank_used), dim3(256), 0, (hipStream_t) nullptr,
+              (const double*)pc.L, s->permuted ? (const int*)s->perm : (const int*)nullptr, s->n, L_dev);
+    RL_HIP(hipGetLastError());
+    RL_HIP(hipDeviceSynchronize());
+    return RL_OK;
+}
+
+// (probe hook, tools/pivchol_probe.py: host milliseconds of the last build -- diagonal; the k
+// products and step kernels; Gram matrix and host maps)
+extern "C" int rl_ski_pivchol_build_ms(rl_ski* s, double* out3) {
+    if (!s || !out3) return fail(RL_EINVAL, "rl_ski_pivchol_build_ms: NULL argument");
+    out3[0] = s->pc.build_ms[0];
+    out3[1] = s->pc.build_ms[1];
+    out3[2] = s->pc.build_ms[3];
     return RL_OK;
 }
 

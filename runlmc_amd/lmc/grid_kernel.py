@@ -269,6 +269,9 @@ class FactoredInverse(Matrix):
 
     def matmat_device(self, X):
         if not self.exact:
+            if self._skiop.factor_mode == 4:
+                # (the pivoted-Cholesky preconditioner: one application, rl_ski_precond_apply)
+                return self._skiop.precond_apply(X.contiguous())
             raise NotImplementedError('this preconditioner is applied inside rl_solve_pcg only')
         return solve_direct(self._skiop, X.contiguous(), tol=np.finfo(np.float64).max,
                             max_refine=0)[0]
@@ -350,10 +353,11 @@ class LMCOperator(SumMatrix):
 
 
 def gen_grid_kernel(fk, grid_dists, interpolants, lens_per_output,
-                    device_index=0, reference_slfm_identity=False):
+                    device_index=0, reference_slfm_identity=False, precond_rank=0):
     """(K~, {active_dim: GridKernel}) exactly as the reference returns them
     (grid_kernel.py:49-74): one GridKernel per active-dimension set, summed
-    with the noise."""
+    with the noise.  precond_rank > 0 opts in to the pivoted-Cholesky preconditioner of that
+    rank for operators without a polynomial factorisation (SkiOp.set_pivchol)."""
     grid_kerns = {}
     for active_dim in fk.active_dims:
         W, WT = interpolants[active_dim]
@@ -363,4 +367,6 @@ def gen_grid_kernel(fk, grid_dists, interpolants, lens_per_output,
             reference_slfm_identity=reference_slfm_identity)
     noise = Diag(np.repeat(fk.noise, lens_per_output))
     K = LMCOperator(list(grid_kerns.values()), noise, fk.noise, lens_per_output)
+    if precond_rank:
+        K.device_operator().set_pivchol(precond_rank)
     return K, grid_kerns

@@ -67,7 +67,7 @@ class InterpolatedLLGP:
                  name='lmc', metrics=False, prediction='on-the-fly',
                  max_procs=None, trace_iterations=15, tolerance=1e-4,
                  functional_kernel=None, group=None, device_index=0, device_probes=None,
-                 variance_batch=None):
+                 variance_batch=None, precond_rank=0):
         self.name = name
         self.input_dim, self.output_dim = self._validate_io(Xs, Ys)
         self.normalizer = None
@@ -95,6 +95,15 @@ class InterpolatedLLGP:
                                  .format(variance_batch))
             variance_batch = int(variance_batch)
         self.variance_batch = variance_batch
+        # precond_rank: 0 (the default) changes nothing; 1 .. 256 opts in to the pivoted-Cholesky
+        # preconditioner of that rank for operators without a polynomial factorisation (2-D and 3-D
+        # grids, several active-dimension sets, more than 16 outputs: SkiOp.set_pivchol) -- the
+        # operator then has a ``preconditioner`` and its solves run preconditioned CG
+        if (isinstance(precond_rank, bool) or not isinstance(precond_rank, (int, np.integer))
+                or not 0 <= precond_rank <= 256):
+            raise ValueError('precond_rank must be an integer in 0 .. 256, got {!r}'
+                             .format(precond_rank))
+        self.precond_rank = int(precond_rank)
         # (the residual rule of the tiled solves: Iterative.solve's default, which the host
         # path's solves run with)
         self.variance_tolerance = 1e-4
@@ -248,7 +257,7 @@ class InterpolatedLLGP:
         if self._K is None:
             self._K, self._grid_kernels = gen_grid_kernel(
                 fk, self.lags, self.interpolants, lens,
-                device_index=self._device_index)
+                device_index=self._device_index, precond_rank=self.precond_rank)
         else:
             # same grid and interpolants: only spectra, factors and noise change
             for ad, gk in self._grid_kernels.items():
