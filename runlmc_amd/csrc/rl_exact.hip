@@ -11,42 +11,35 @@ struct rl_exact {
     int maxf = 1;                   // most factors of any kernel (3 with any cosine leaf): 1 runs the kernels' <1> bodies
     int sep = 0;                    // rl_exact_set_separable: cols holds the leaves' column lists, the kernels run <., true>
     int state = EX_EMPTY;
-    double* A = nullptr;            // n x n
-    double* X = nullptr;            // n x P
-    int* out_of = nullptr;          // n: output of each row
-    int* bounds = nullptr;          // D + 1 row offsets of the outputs
-    int* kinds = nullptr;           // descriptors (rl_exact.h: ex_desc; capacity EX_MAX_SLOT kernels)
-    double* prm = nullptr;
-    int* cols = nullptr;            // [Q][EX_MAX_COLS], or [Q][EX_MAX_FACT][EX_MAX_COLS] when sep
-    int* dslot = nullptr;
-    double* Bm = nullptr;           // Q x D x D
-    double* noise = nullptr;        // D
-    double* logd = nullptr;         // n
-    double* scal = nullptr;         // 1
-    int* flag = nullptr;            // first bad pivot
-    double* ws = nullptr;           // split-k partial sums / gradient partials
-    size_t ws_cap = 0;
-    int* tiles = nullptr;           // gradient workgroups (r0, c0, a, b)
-    int* pair_start = nullptr;
+    DevBuf<double> A;               // n x n
+    DevBuf<double> X;               // n x P
+    DevBuf<int> out_of;             // n: output of each row
+    DevBuf<int> bounds;             // D + 1 row offsets of the outputs
+    DevBuf<int> kinds;              // descriptors (rl_exact.h: ex_desc; capacity EX_MAX_SLOT kernels)
+    DevBuf<double> prm;
+    DevBuf<int> cols;               // [Q][EX_MAX_COLS], or [Q][EX_MAX_FACT][EX_MAX_COLS] when sep
+    DevBuf<int> dslot;
+    DevBuf<double> Bm;              // Q x D x D
+    DevBuf<double> noise;           // D
+    DevBuf<double> logd;            // n
+    DevBuf<double> scal;            // 1
+    DevBuf<int> flag;               // first bad pivot
+    DevBuf<double> ws;              // split-k partial sums / gradient partials
+    DevBuf<int> tiles;              // gradient workgroups (r0, c0, a, b)
+    DevBuf<int> pair_start;
     int ntiles = 0;
-    double* gout = nullptr;         // gradient sums
-    double* xt = nullptr;           // test rows of rl_exact_cross_dev (kept between calls)
-    int* ot = nullptr;
-    size_t xt_cap = 0, ot_cap = 0;
+    DevBuf<double> gout;            // gradient sums
+    DevBuf<double> xt;              // test rows of rl_exact_cross_dev (kept between calls)
+    DevBuf<int> ot;
     std::vector<int> lens, hbounds;
 };
 
 static int ex_ws(rl_exact* h, size_t doubles) {
-    if (doubles <= h->ws_cap) return RL_OK;
-    if (h->ws) RL_HIP(hipFree(h->ws));
-    h->ws = nullptr;
-    h->ws_cap = 0;
-    if (hipMalloc((void**)&h->ws, doubles * sizeof(double)) != hipSuccess) {
+    if (h->ws.reserve(doubles) != RL_OK) {
         (void)hipGetLastError();
         return fail(RL_ENOMEM, "rl_exact: no device memory for a workspace of " +
                                    std::to_string(doubles * 8 >> 20) + " MB");
     }
-    h->ws_cap = doubles;
     return RL_OK;
 }
 
@@ -159,20 +152,19 @@ extern "C" int rl_exact_create(int device, int n, int P, rl_exact** out) {
     hipDeviceProp_t prop;
     RL_HIP(hipGetDeviceProperties(&prop, device));
     h->ncu = std::max(1, prop.multiProcessorCount);
-    RL_HIP(hipMalloc((void**)&h->X, (size_t)n * P * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&h->out_of, (size_t)n * sizeof(int)));
-    RL_HIP(hipMalloc((void**)&h->bounds, (EX_MAX_D + 1) * sizeof(int)));
-    RL_HIP(hipMalloc((void**)&h->kinds, EX_MAX_SLOT * sizeof(int)));
-    RL_HIP(hipMalloc((void**)&h->prm, 2 * EX_PRM2 * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&h->cols, EX_MAX_SLOT * EX_LEAF_COLS * sizeof(int)));
-    RL_HIP(hipMalloc((void**)&h->dslot, EX_MAX_SLOT * sizeof(int)));
-    RL_HIP(hipMalloc((void**)&h->Bm, (size_t)EX_MAX_SLOT * EX_MAX_D * EX_MAX_D * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&h->noise, EX_MAX_D * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&h->logd, (size_t)n * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&h->scal, sizeof(double)));
-    RL_HIP(hipMalloc((void**)&h->flag, sizeof(int)));
-    RL_HIP(hipMalloc((void**)&h->gout,
-                     ((size_t)EX_MAX_SLOT * EX_MAX_D * EX_MAX_D + EX_MAX_D) * sizeof(double)));
+    RL_TRY(h->X.reserve((size_t)n * P));
+    RL_TRY(h->out_of.reserve((size_t)n));
+    RL_TRY(h->bounds.reserve(EX_MAX_D + 1));
+    RL_TRY(h->kinds.reserve(EX_MAX_SLOT));
+    RL_TRY(h->prm.reserve(2 * EX_PRM2));
+    RL_TRY(h->cols.reserve(EX_MAX_SLOT * EX_LEAF_COLS));
+    RL_TRY(h->dslot.reserve(EX_MAX_SLOT));
+    RL_TRY(h->Bm.reserve((size_t)EX_MAX_SLOT * EX_MAX_D * EX_MAX_D));
+    RL_TRY(h->noise.reserve(EX_MAX_D));
+    RL_TRY(h->logd.reserve((size_t)n));
+    RL_TRY(h->scal.reserve(1));
+    RL_TRY(h->flag.reserve(1));
+    RL_TRY(h->gout.reserve((size_t)EX_MAX_SLOT * EX_MAX_D * EX_MAX_D + EX_MAX_D));
     (void)hipFuncSetAttribute((const void*)k_ex_grad_tiles<1>,
                               hipFuncAttributeMaxDynamicSharedMemorySize,
                               (EX_MAX_SLOT + 1) * 256 * (int)sizeof(double));
@@ -189,11 +181,6 @@ extern "C" int rl_exact_create(int device, int n, int P, rl_exact** out) {
 extern "C" int rl_exact_destroy(rl_exact* h) {
     if (!h) return RL_OK;
     (void)hipSetDevice(h->device);
-    for (void* p : {(void*)h->A, (void*)h->X, (void*)h->out_of, (void*)h->bounds, (void*)h->kinds,
-                    (void*)h->prm, (void*)h->cols, (void*)h->dslot, (void*)h->Bm, (void*)h->noise,
-                    (void*)h->logd, (void*)h->scal, (void*)h->flag, (void*)h->ws, (void*)h->tiles,
-                    (void*)h->pair_start, (void*)h->gout, (void*)h->xt, (void*)h->ot})
-        if (p) (void)hipFree(p);
     delete h;
     return RL_OK;
 }
@@ -291,12 +278,10 @@ static int ex_set(rl_exact* h, const char* what, const double* X, const int* len
                     }
                 ps.push_back((int)tl.size() / 4);
             }
-        if (h->tiles) RL_HIP(hipFree(h->tiles));
-        if (h->pair_start) RL_HIP(hipFree(h->pair_start));
-        h->tiles = nullptr;
-        h->pair_start = nullptr;
-        RL_TRY(upload(&h->tiles, tl));
-        RL_TRY(upload(&h->pair_start, ps));
+        h->tiles.reset();
+        h->pair_start.reset();
+        RL_TRY(h->tiles.upload(tl));
+        RL_TRY(h->pair_start.upload(ps));
         h->ntiles = (int)tl.size() / 4;
         h->lens.assign(lens, lens + D);
     }
@@ -400,9 +385,8 @@ extern "C" int rl_exact_assemble(rl_exact* h) {
             return fail(RL_ENOMEM, "rl_exact: the " + std::to_string(n) + " x " + std::to_string(n) +
                                        " matrix needs " + std::to_string(bytes >> 20) + " MB, " +
                                        std::to_string(fr >> 20) + " MB free");
-        if (hipMalloc((void**)&h->A, bytes) != hipSuccess) {
+        if (h->A.reserve((size_t)n * n) != RL_OK) {
             (void)hipGetLastError();
-            h->A = nullptr;
             return fail(RL_ENOMEM, "rl_exact: hipMalloc of the n x n matrix failed");
         }
     }
@@ -471,7 +455,8 @@ extern "C" int rl_exact_solve(rl_exact* h, const double* B, double* X, int nrhs,
 }
 
 // test rows on the device: X (nt x P) and their outputs
-static int ex_upload_test(rl_exact* h, const double* Xt, const int* tlens, double** dX, int** dO, int* nt) {
+static int ex_upload_test(rl_exact* h, const double* Xt, const int* tlens, DevBuf<double>* dX,
+                          DevBuf<int>* dO, int* nt) {
     long long total = 0;
     for (int d = 0; d < h->D; ++d) {
         if (tlens[d] < 0) return fail(RL_EINVAL, "rl_exact: negative test length");
@@ -482,19 +467,14 @@ static int ex_upload_test(rl_exact* h, const double* Xt, const int* tlens, doubl
     std::vector<int> o((size_t)total);
     for (int d = 0, i = 0; d < h->D; ++d)
         for (int k = 0; k < tlens[d]; ++k) o[i++] = d;
-    RL_HIP(hipMalloc((void**)dX, std::max<size_t>(1, (size_t)total * h->P) * sizeof(double)));
-    RL_HIP(hipMalloc((void**)dO, std::max<size_t>(1, (size_t)total) * sizeof(int)));
+    RL_TRY(dX->reserve(std::max<size_t>(1, (size_t)total * h->P)));
+    RL_TRY(dO->reserve(std::max<size_t>(1, (size_t)total)));
     if (total) {
         RL_HIP(hipMemcpy(*dX, Xt, (size_t)total * h->P * sizeof(double), hipMemcpyHostToDevice));
         RL_HIP(hipMemcpy(*dO, o.data(), (size_t)total * sizeof(int), hipMemcpyHostToDevice));
     }
     return RL_OK;
 }
-
-struct ExTmp {
-    void* p[3] = {nullptr, nullptr, nullptr};
-    ~ExTmp() { for (void* q : p) if (q) (void)hipFree(q); }
-};
 
 // rows of the cross-covariance per chunk: at most 256 MB of them on the device at once
 static int ex_chunk_rows(const rl_exact* h) {
@@ -506,26 +486,27 @@ static int ex_cross_rows(rl_exact* h, const double* Xt, const int* tlens, const 
                          double* out_host, double* var_out) {
     if (h->state < EX_SET) return fail(RL_EINVAL, "rl_exact: no parameters (rl_exact_set)");
     RL_HIP(hipSetDevice(h->device));
-    ExTmp t;
+    DevBuf<double> tX, tV;          // temporaries of this call
+    DevBuf<int> tO;
     int nt = 0;
     if (Xt) {
-        RL_TRY(ex_upload_test(h, Xt, tlens, (double**)&t.p[0], (int**)&t.p[1], &nt));
+        RL_TRY(ex_upload_test(h, Xt, tlens, &tX, &tO, &nt));
     } else {
         nt = h->n;
     }
     if (nt == 0) return RL_OK;
     const int rows = std::min(nt, ex_chunk_rows(h));
-    if (hipMalloc(&t.p[2], (size_t)rows * h->n * sizeof(double)) != hipSuccess) {
+    if (tV.reserve((size_t)rows * h->n) != RL_OK) {
         (void)hipGetLastError();
         return fail(RL_ENOMEM, "rl_exact: no device memory for the cross-covariance");
     }
-    double* V = (double*)t.p[2];
+    double* V = tV;
     double* norms = nullptr;
     if (var_out) RL_TRY(ex_ws(h, (size_t)rows));
     for (int r0 = 0; r0 < nt; r0 += rows) {
         const int nr = std::min(rows, nt - r0);
-        const double* xa = Xt ? (const double*)t.p[0] + (long long)r0 * h->P : h->X + (long long)r0 * h->P;
-        const int* oa = Xt ? (const int*)t.p[1] + r0 : h->out_of + r0;
+        const double* xa = Xt ? tX + (long long)r0 * h->P : h->X + (long long)r0 * h->P;
+        const int* oa = Xt ? tO + r0 : h->out_of + r0;
         RL_TRY(ex_cross(h, 0, V, xa, oa, nr, noise, r0));
         if (var_out) {
             RL_TRY(ex_trsv(h, 0, V, nr, true, false));
@@ -599,20 +580,8 @@ extern "C" int rl_exact_cross_dev(rl_exact* h, const double* Xtest, const int* t
             begin = end;
         }
     }
-    if (h->xt_cap < (size_t)nrows * P) {
-        if (h->xt) RL_HIP(hipFree(h->xt));
-        h->xt = nullptr;
-        h->xt_cap = 0;
-        RL_HIP(hipMalloc((void**)&h->xt, (size_t)nrows * P * sizeof(double)));
-        h->xt_cap = (size_t)nrows * P;
-    }
-    if (h->ot_cap < (size_t)nrows) {
-        if (h->ot) RL_HIP(hipFree(h->ot));
-        h->ot = nullptr;
-        h->ot_cap = 0;
-        RL_HIP(hipMalloc((void**)&h->ot, (size_t)nrows * sizeof(int)));
-        h->ot_cap = (size_t)nrows;
-    }
+    RL_TRY(h->xt.reserve((size_t)nrows * P));
+    RL_TRY(h->ot.reserve((size_t)nrows));
     // the host rows are consumed before the call returns; the kernel stays queued
     RL_HIP(hipMemcpyAsync(h->xt, Xtest + (long long)row0 * P, (size_t)nrows * P * sizeof(double),
                           hipMemcpyHostToDevice, st));
@@ -661,13 +630,12 @@ extern "C" int rl_exact_invert(rl_exact* h) {
     const hipStream_t st = 0;
     // L^-1 in place, last block column first (LAPACK dtrtri, lower):  W_jj = L_jj^-1,
     // W21 = -(W22 L21) W_jj  (W22 already inverted; tmp = n x 64 beside the matrix)
-    double* tmp = nullptr;
-    if (hipMalloc((void**)&tmp, (size_t)n * EX_T * sizeof(double)) != hipSuccess) {
+    DevBuf<double> panel;
+    if (panel.reserve((size_t)n * EX_T) != RL_OK) {
         (void)hipGetLastError();
         return fail(RL_ENOMEM, "rl_exact_invert: no device memory for an n x 64 panel");
     }
-    ExTmp guard;
-    guard.p[0] = tmp;
+    double* tmp = panel;
     for (int j = nb - 1; j >= 0; --j) {
         const int j0 = j * EX_T, nj = std::min(EX_T, n - j0), r0 = j0 + nj, rest = n - r0;
         RL_LAUNCH(k_ex_trtri_diag, dim3(1), dim3(64), kTileLds, st, A, ld, j0, nj);

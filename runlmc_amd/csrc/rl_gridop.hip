@@ -292,10 +292,8 @@ static size_t lds_rows(int N2, int cols) {
 
 static int ensure_workspace(rl_gridop* g, size_t pairs) {
     if (pairs <= g->T_pairs) return RL_OK;
-    if (g->T) RL_HIP(hipFree(g->T));
-    g->T = nullptr;
     g->T_pairs = 0;
-    RL_HIP(hipMalloc((void**)&g->T, pairs * g->D * (size_t)g->L * sizeof(cplx)));
+    RL_TRY(g->T.renew(pairs * g->D * (size_t)g->L));
     g->T_pairs = pairs;
     return RL_OK;
 }
@@ -489,7 +487,7 @@ extern "C" int rl_gridop_create_3d(int device, int D, int m0, int m1, int m2, in
     // (exact at the quarter turns, so that N0 = 4 is exact arithmetic)
     tw[0] = 1.0; tw[1] = 0.0;
     tw[2 * (g->N0 / 4)] = 0.0; tw[2 * (g->N0 / 4) + 1] = -1.0;
-    RL_TRY(upload(&g->lead_tw, tw));
+    RL_TRY(g->lead_tw.upload(tw));
     *out = guard.release();
     return RL_OK;
 }
@@ -540,7 +538,7 @@ static int gridop_create_impl(int device, int D, int m, int m1, int m2, int max_
         w->rowsB = w->child->rowsB;
         w->chunk_pairs = w->child->chunk_pairs;
         w->max_fac = max_tops * D;
-        RL_HIP(hipMalloc((void**)&w->wide_B, (size_t)max_tops * D * D * sizeof(double)));
+        RL_TRY(w->wide_B.reserve((size_t)max_tops * D * D));
         *out = wguard.release();
         return RL_OK;
     }
@@ -632,27 +630,27 @@ static int gridop_create_impl(int device, int D, int m, int m1, int m2, int max_
     g->h_freq2 = position_to_freq(g->plan2);
 
     int rc;
-    if ((rc = upload(&g->tw1, unity_table(g->N1, 1, g->N1))) != RL_OK) return rc;
-    if ((rc = upload(&g->tw2, unity_table(g->N2, 1, g->N2))) != RL_OK) return rc;
+    if ((rc = g->tw1.upload(unity_table(g->N1, 1, g->N1))) != RL_OK) return rc;
+    if ((rc = g->tw2.upload(unity_table(g->N2, 1, g->N2))) != RL_OK) return rc;
     const int shift = l / 2;
-    if ((rc = upload(&g->twlo, unity_table(1L << shift, 1, L))) != RL_OK) return rc;
-    if ((rc = upload(&g->twhi, unity_table(((long)L + (1L << shift) - 1) >> shift, 1L << shift,
+    if ((rc = g->twlo.upload(unity_table(1L << shift, 1, L))) != RL_OK) return rc;
+    if ((rc = g->twhi.upload(unity_table(((long)L + (1L << shift) - 1) >> shift, 1L << shift,
                                            L))) != RL_OK) return rc;
-    if ((rc = upload(&g->freq1, g->h_freq1)) != RL_OK) return rc;
-    g->twl.lo = m1 == 0 ? g->twlo : nullptr;   // 2-D: no inter-step twiddle
+    if ((rc = g->freq1.upload(g->h_freq1)) != RL_OK) return rc;
+    g->twl.lo = m1 == 0 ? g->twlo.get() : nullptr;   // 2-D: no inter-step twiddle
     g->twl.hi = g->twhi;
     g->twl.shift = shift;
     g->twl.mask = (1 << shift) - 1;
 
     g->max_fac = max_tops * D;
-    RL_HIP(hipMalloc((void**)&g->tops, (size_t)max_tops * m * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&g->spec, (size_t)max_tops * L * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&g->facA, (size_t)g->max_fac * D * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&g->facW, (size_t)g->max_fac * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&g->facQ, (size_t)g->max_fac * sizeof(int)));
-    RL_HIP(hipMalloc((void**)&g->kappa, (size_t)max_tops * D * sizeof(double)));
+    RL_TRY(g->tops.reserve((size_t)max_tops * m));
+    RL_TRY(g->spec.reserve((size_t)max_tops * L));
+    RL_TRY(g->facA.reserve((size_t)g->max_fac * D));
+    RL_TRY(g->facW.reserve((size_t)g->max_fac));
+    RL_TRY(g->facQ.reserve((size_t)g->max_fac));
+    RL_TRY(g->kappa.reserve((size_t)max_tops * D));
     std::vector<double> ones(D, 1.0);
-    if ((rc = upload(&g->ones, ones)) != RL_OK) return rc;
+    if ((rc = g->ones.upload(ones)) != RL_OK) return rc;
 
     // intermediates of one chunk: large enough that a launch's tail does not
     // matter, small enough to sit in the 256 MiB Infinity Cache (measured: C2,
@@ -686,8 +684,8 @@ static int gridop_create_impl(int device, int D, int m, int m1, int m2, int max_
         const size_t lds = ((size_t)L * (D | 1) + L) * sizeof(cplx);
         if (lds <= kLdsHard) {
             g->planL = make_plan(L);
-            if ((rc = upload(&g->twL, unity_table(L, 1, L))) != RL_OK) return rc;
-            RL_HIP(hipMalloc((void**)&g->spec1, (size_t)max_tops * L * sizeof(double)));
+            if ((rc = g->twL.upload(unity_table(L, 1, L))) != RL_OK) return rc;
+            RL_TRY(g->spec1.reserve((size_t)max_tops * L));
             g->lds1 = lds;
             g->thr1 = (size_t)D * L >= 4096 ? 512 : 256;
             g->v1p = true;
@@ -703,19 +701,6 @@ extern "C" int rl_gridop_destroy(rl_gridop* g) {
     (void)hipSetDevice(g->device);
     if (g->child) (void)rl_gridop_destroy(g->child);
     for (rl_gridop* k : g->kids) (void)rl_gridop_destroy(k);
-    if (g->lead_tw) (void)hipFree(g->lead_tw);
-    if (g->lead_x) (void)hipFree(g->lead_x);
-    if (g->lead_y) (void)hipFree(g->lead_y);
-    if (g->wide_B) (void)hipFree(g->wide_B);
-    if (g->wide_Z) (void)hipFree(g->wide_Z);
-    void* ptrs[] = {g->tw1, g->tw2, g->twlo, g->twhi, g->freq1, g->tops, g->spec,
-                    g->facA, g->facW, g->facQ, g->kappa, g->ones, g->T,
-                    g->T2[0], g->T2[1], g->T2[2], g->twL, g->spec1, g->mixtab, g->lr_beta, g->lr_nu, g->lr_phiJ, g->lr_stat, g->lr_M,
-                    g->lr_B, g->lr_eye, g->lr_part, g->lr_zhat, g->lr_scr, g->lr_pw, g->lr_sel, g->lr_Cc, g->lr_Bc, g->lr_Mf, g->lr_spart, g->lr_Cx,
-                    g->sf_tops, g->sf_blob, g->sf_blob_top, g->sf_pwp, g->sf_pw, g->sf_kappa, g->sf_facA, g->sf_facAW, g->sf_facJ,
-                    g->sf_E, g->sf_Cin, g->sf_next};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     if (g->ev_fork) (void)hipEventDestroy(g->ev_fork);
     for (int i = 0; i < 3; ++i) {
         if (g->ev_join[i]) (void)hipEventDestroy(g->ev_join[i]);
@@ -878,10 +863,8 @@ static int set_factors(rl_gridop* g, const std::vector<double>& A, const std::ve
     if (g->rows3 && nfac <= RL_MIXF) {
         const size_t rows = (size_t)g->D + nfac;
         if (rows > g->mixtab_rows) {
-            if (g->mixtab) RL_HIP(hipFree(g->mixtab));
-            g->mixtab = nullptr;
             g->mixtab_rows = 0;
-            RL_HIP(hipMalloc((void**)&g->mixtab, rows * (size_t)g->L * sizeof(double)));
+            RL_TRY(g->mixtab.renew(rows * (size_t)g->L));
             g->mixtab_rows = rows;
         }
         MixParams mp{g->Q, g->nfac, g->spec, g->facA, g->facW, g->facQ, g->kappa, nullptr, nullptr};
@@ -1417,13 +1400,10 @@ static int product_streams() { return 2; }
 static int prepare_two_streams(rl_gridop* g, size_t chunk) {
     const int want = product_streams() - 1;
     if (g->T2_pairs < chunk || g->nside < want) {
-        for (int i = 0; i < 3; ++i) {
-            if (g->T2[i]) RL_HIP(hipFree(g->T2[i]));
-            g->T2[i] = nullptr;
-        }
+        for (int i = 0; i < 3; ++i) g->T2[i].reset();
         g->T2_pairs = 0;
         for (int i = 0; i < want; ++i)
-            RL_HIP(hipMalloc((void**)&g->T2[i], chunk * g->D * (size_t)g->L * sizeof(cplx)));
+            RL_TRY(g->T2[i].reserve(chunk * g->D * (size_t)g->L));
         g->T2_pairs = chunk;
     }
     if (!g->ev_fork) RL_HIP(hipEventCreateWithFlags(&g->ev_fork, hipEventDisableTiming));
@@ -1484,9 +1464,9 @@ static int lr_make_basis(rl_gridop* g) {
             cur[n] = nxt[n] / bj;
         }
     }
-    RL_TRY(upload(&g->lr_phiJ, phiJ));
-    RL_TRY(upload(&g->lr_beta, beta));
-    RL_TRY(upload(&g->lr_nu, nu));
+    RL_TRY(g->lr_phiJ.upload(phiJ));
+    RL_TRY(g->lr_beta.upload(beta));
+    RL_TRY(g->lr_nu.upload(nu));
     g->lr_hnu = nu;
     return RL_OK;
 }
@@ -1526,20 +1506,8 @@ static size_t lr_part_need(const rl_gridop* g, int nvec) {
 int lr_reserve(rl_gridop* g, int nvec) {
     const size_t rows = (size_t)nvec * g->D;
     const size_t need_part = lr_part_need(g, nvec), need_z = rows * RL_LR_RMAX;
-    if (g->lr_part_cap < need_part) {
-        if (g->lr_part) RL_HIP(hipFree(g->lr_part));
-        g->lr_part = nullptr;
-        g->lr_part_cap = 0;
-        RL_HIP(hipMalloc((void**)&g->lr_part, need_part * sizeof(double)));
-        g->lr_part_cap = need_part;
-    }
-    if (g->lr_zhat_cap < need_z) {
-        if (g->lr_zhat) RL_HIP(hipFree(g->lr_zhat));
-        g->lr_zhat = nullptr;
-        g->lr_zhat_cap = 0;
-        RL_HIP(hipMalloc((void**)&g->lr_zhat, need_z * sizeof(double)));
-        g->lr_zhat_cap = need_z;
-    }
+    RL_TRY(g->lr_part.reserve(need_part));
+    RL_TRY(g->lr_zhat.reserve(need_z));
     return RL_OK;
 }
 
@@ -1796,25 +1764,13 @@ static size_t sf_need_Cin(const rl_gridop* g, int nvec, int nchan, int NS) {
     return (size_t)sf_nchunks(g) * nvec * nchan * 2 * NS;
 }
 static bool sf_ready(const rl_gridop* g, int nvec, int NF, int nfac, int NS) {
-    return g->sf_E_cap >= sf_need_E(g, nvec, NF, NS) &&
-           g->sf_Cin_cap >= sf_need_Cin(g, nvec, g->D * NF + nfac, NS);
+    return g->sf_E.cap >= sf_need_E(g, nvec, NF, NS) &&
+           g->sf_Cin.cap >= sf_need_Cin(g, nvec, g->D * NF + nfac, NS);
 }
 static int sf_reserve(rl_gridop* g, int nvec, int NF, int nfac, int NS) {
     const size_t needE = sf_need_E(g, nvec, NF, NS), needC = sf_need_Cin(g, nvec, g->D * NF + nfac, NS);
-    if (g->sf_E_cap < needE) {
-        if (g->sf_E) RL_HIP(hipFree(g->sf_E));
-        g->sf_E = nullptr;
-        g->sf_E_cap = 0;
-        RL_HIP(hipMalloc((void**)&g->sf_E, needE * sizeof(double)));
-        g->sf_E_cap = needE;
-    }
-    if (g->sf_Cin_cap < needC) {
-        if (g->sf_Cin) RL_HIP(hipFree(g->sf_Cin));
-        g->sf_Cin = nullptr;
-        g->sf_Cin_cap = 0;
-        RL_HIP(hipMalloc((void**)&g->sf_Cin, needC * sizeof(double)));
-        g->sf_Cin_cap = needC;
-    }
+    RL_TRY(g->sf_E.reserve(needE));
+    RL_TRY(g->sf_Cin.reserve(needC));
     return RL_OK;
 }
 // (NS: states per direction; two-state launches keep the three-state size)
@@ -2081,28 +2037,27 @@ static int lr_verify(rl_gridop* g, const std::vector<char>& want, std::vector<ch
     if (!g->lr_phiJ) {
         RL_TRY(lr_make_basis(g));
         // verdict records in front of C, so that one copy brings both back
-        double* cs = nullptr;
-        RL_HIP(hipMalloc((void**)&cs, (size_t)g->max_tops * (RL_LR_STATW + RL_LR_RMAX * RL_LR_RMAX) * sizeof(double)));
+        RL_TRY(g->lr_stat.reserve((size_t)g->max_tops * (RL_LR_STATW + RL_LR_RMAX * RL_LR_RMAX)));
+        double* cs = g->lr_stat;
         // (zeros: the grouped power iteration multiplies the C of tops that are no candidates by a
         // zero coupling -- they have to be finite)
         RL_HIP(hipMemset(cs, 0, (size_t)g->max_tops * (RL_LR_STATW + RL_LR_RMAX * RL_LR_RMAX) * sizeof(double)));
-        g->lr_stat = cs;
         g->lr_C = cs + (size_t)g->max_tops * RL_LR_STATW;
-        RL_HIP(hipMalloc((void**)&g->lr_Cc, (size_t)g->max_tops * RL_LR_RMAX * RL_LR_RMAX * sizeof(double)));
-        RL_HIP(hipMalloc((void**)&g->lr_B, (size_t)g->max_tops * D * D * sizeof(double)));
-        RL_HIP(hipMalloc((void**)&g->lr_Bc, (size_t)g->max_tops * D * D * sizeof(double)));
+        RL_TRY(g->lr_Cc.reserve((size_t)g->max_tops * RL_LR_RMAX * RL_LR_RMAX));
+        RL_TRY(g->lr_B.reserve((size_t)g->max_tops * D * D));
+        RL_TRY(g->lr_Bc.reserve((size_t)g->max_tops * D * D));
         std::vector<double> eye((size_t)D * D, 0.0);
         for (int a = 0; a < D; ++a) eye[(size_t)a * D + a] = 1.0;
-        RL_TRY(upload(&g->lr_eye, eye));
+        RL_TRY(g->lr_eye.upload(eye));
         // scratch: a fixed random vector, two results, the packed T Phi block
         const size_t nvr = (RL_LR_RMAX + RL_LR_EXTRA + D - 1) / D;
-        RL_HIP(hipMalloc((void**)&g->lr_scr, (3 + nvr) * vec * sizeof(double)));
+        RL_TRY(g->lr_scr.reserve((3 + nvr) * vec));
         // power iteration: [v | w], [T v | T w], partial sums
-        RL_HIP(hipMalloc((void**)&g->lr_pw, (4 * vec + 2 * (size_t)RL_LR_PWB * D) * sizeof(double)));
+        RL_TRY(g->lr_pw.reserve((4 * vec + 2 * (size_t)RL_LR_PWB * D)));
         // selector couplings of the grouped power iteration, per group of D candidate tops:
         // kappa [Q][D] | B [Q][D][D] | top of each output row [D] (ints, padded to doubles)
-        RL_HIP(hipMalloc((void**)&g->lr_sel, (size_t)g->max_tops *
-                         ((size_t)g->max_tops * D + (size_t)g->max_tops * D * D + D) * sizeof(double)));
+        RL_TRY(g->lr_sel.reserve((size_t)g->max_tops *
+                                 ((size_t)g->max_tops * D + (size_t)g->max_tops * D * D + D)));
         std::vector<double> xr(vec);
         unsigned long long st = 0x9E3779B97F4A7C15ull;          // fixed seed: same trials every time
         for (size_t i = 0; i < vec; ++i) {
@@ -2362,21 +2317,16 @@ static int forms_setup(rl_gridop* g, const std::vector<double>& A, const std::ve
     if (nfilt) {
         // (each buffer under its own guard: an allocation that fails part-way is retried
         // at the next parameter update instead of leaving later pointers null)
-        auto need = [](void** p, size_t bytes) -> int {
-            if (*p) return RL_OK;
-            RL_HIP(hipMalloc(p, bytes));
-            return RL_OK;
-        };
-        RL_TRY(need((void**)&g->sf_tops, (size_t)g->max_tops * sizeof(SfTop)));
-        RL_TRY(need((void**)&g->sf_next, sizeof(int)));
-        RL_TRY(need((void**)&g->sf_blob, (size_t)sf_blob_doubles(g->max_tops, g->max_fac, D) * sizeof(double)));
-        RL_TRY(need((void**)&g->sf_blob_top, (size_t)g->max_tops * sf_blob_doubles(1, 0, D) * sizeof(double)));
-        RL_TRY(need((void**)&g->sf_pw, (size_t)g->max_tops * (RL_SF_G + 1) * sizeof(double)));
-        RL_TRY(need((void**)&g->sf_pwp, (size_t)g->max_tops * 2 * RL_SF_G * sizeof(double)));
-        RL_TRY(need((void**)&g->sf_kappa, (size_t)g->max_tops * D * sizeof(double)));
-        RL_TRY(need((void**)&g->sf_facA, (size_t)std::max(g->max_fac, 1) * D * sizeof(double)));
-        RL_TRY(need((void**)&g->sf_facAW, (size_t)std::max(g->max_fac, 1) * D * sizeof(double)));
-        RL_TRY(need((void**)&g->sf_facJ, (size_t)std::max(g->max_fac, 1) * sizeof(int)));
+        RL_TRY(g->sf_tops.reserve((size_t)g->max_tops));
+        RL_TRY(g->sf_next.reserve(1));
+        RL_TRY(g->sf_blob.reserve((size_t)sf_blob_doubles(g->max_tops, g->max_fac, D)));
+        RL_TRY(g->sf_blob_top.reserve((size_t)g->max_tops * sf_blob_doubles(1, 0, D)));
+        RL_TRY(g->sf_pw.reserve((size_t)g->max_tops * (RL_SF_G + 1)));
+        RL_TRY(g->sf_pwp.reserve((size_t)g->max_tops * 2 * RL_SF_G));
+        RL_TRY(g->sf_kappa.reserve((size_t)g->max_tops * D));
+        RL_TRY(g->sf_facA.reserve((size_t)std::max(g->max_fac, 1) * D));
+        RL_TRY(g->sf_facAW.reserve((size_t)std::max(g->max_fac, 1) * D));
+        RL_TRY(g->sf_facJ.reserve((size_t)std::max(g->max_fac, 1)));
         std::vector<SfTop> tops(nfilt);
         std::vector<SfBlk> blks(nfilt);
         std::vector<double> pw((size_t)nfilt * (RL_SF_G + 1)), kp((size_t)nfilt * D), fa, faw;
@@ -2455,13 +2405,7 @@ static int forms_setup(rl_gridop* g, const std::vector<double>& A, const std::ve
                                     Mf[((size_t)a * r + i) * Dr + (size_t)b * r + j] +=
                                         bq * g->lr_hnu[i] * g->lr_hnu[j] * g->lr_hC[((size_t)q * r + i) * r + j];
                         }
-                if (g->lr_Mf_cap < Mf.size()) {
-                    if (g->lr_Mf) RL_HIP(hipFree(g->lr_Mf));
-                    g->lr_Mf = nullptr;
-                    g->lr_Mf_cap = 0;
-                    RL_HIP(hipMalloc((void**)&g->lr_Mf, Mf.size() * sizeof(double)));
-                    g->lr_Mf_cap = Mf.size();
-                }
+                RL_TRY(g->lr_Mf.reserve(Mf.size()));
                 RL_HIP(hipMemcpy(g->lr_Mf, Mf.data(), Mf.size() * sizeof(double), hipMemcpyHostToDevice));
                 g->lr_Mf_ok = true;
             }
@@ -2486,7 +2430,7 @@ static int forms_setup(rl_gridop* g, const std::vector<double>& A, const std::ve
                         for (int b = 0; b < D; ++b)
                             for (int j = 0; j < r; ++j)
                                 M[(((size_t)a * r + i) * D + b) * r + j] *= hnu[i] * hnu[j];
-                if (!g->lr_M) RL_HIP(hipMalloc((void**)&g->lr_M, M.size() * sizeof(double)));
+                if (!g->lr_M) RL_TRY(g->lr_M.reserve(M.size()));
                 RL_HIP(hipMemcpy(g->lr_M, M.data(), M.size() * sizeof(double), hipMemcpyHostToDevice));
             }
             return RL_OK;
@@ -2550,7 +2494,7 @@ int lr_all_coeffs(rl_gridop* g, int R, std::vector<double>* hC, std::vector<char
         RL_TRY(lr_verify(g, none, &pass));
     }
     if (g->lr_np == 0) g->lr_r = R;
-    if (!g->lr_Cx) RL_HIP(hipMalloc((void**)&g->lr_Cx, (size_t)RL_LR_RMAX * RL_LR_RMAX * sizeof(double)));
+    if (!g->lr_Cx) RL_TRY(g->lr_Cx.reserve((size_t)RL_LR_RMAX * RL_LR_RMAX));
     hC->assign((size_t)Q * R * R, 0.0);
     exact->assign(Q, 0);
     captured->assign(Q, 0.0);
@@ -2632,13 +2576,7 @@ k_wide_mix(const double* __restrict__ Z, const double* __restrict__ B, int D, in
 
 static int wide_reserve(rl_gridop* g, int nvec) {
     const size_t need = (size_t)nvec * g->D * g->m;
-    if (g->wide_Z_cap >= need) return RL_OK;
-    if (g->wide_Z) RL_HIP(hipFree(g->wide_Z));
-    g->wide_Z = nullptr;
-    g->wide_Z_cap = 0;
-    RL_HIP(hipMalloc((void**)&g->wide_Z, need * sizeof(double)));
-    g->wide_Z_cap = need;
-    return RL_OK;
+    return g->wide_Z.reserve(need);
 }
 
 // the operator: one single-top product of the child per top row, one mix pass each
@@ -2649,7 +2587,7 @@ static int wide_mvm(rl_gridop* g, const double* X, double* Y, int nvec, hipStrea
     if (X == Y) return fail(RL_EINVAL, "X and Y may not alias");
     if (g->Q < 1) return fail(RL_EINVAL, "grid operator has no parameters yet");
     RL_HIP(hipSetDevice(g->device));
-    if (g->wide_Z_cap < (size_t)nvec * g->D * g->m) {
+    if (g->wide_Z.cap < (size_t)nvec * g->D * g->m) {
         if (stream_capturing(stream))
             return fail(RL_EINVAL, "wide operator: workspace not reserved before a capture");
         RL_TRY(wide_reserve(g, nvec));
@@ -2682,12 +2620,11 @@ static int lead_reserve(rl_gridop* g, int nvec) {
     if (g->lead_cap < (size_t)nvec) {
         const size_t F = g->kids.size(), M = (size_t)g->m / g->m0;
         const size_t need = F * 2 * (size_t)nvec * g->D * M;
-        if (g->lead_x) RL_HIP(hipFree(g->lead_x));
-        if (g->lead_y) RL_HIP(hipFree(g->lead_y));
-        g->lead_x = g->lead_y = nullptr;
+        g->lead_x.reset();
+        g->lead_y.reset();
         g->lead_cap = 0;
-        RL_HIP(hipMalloc((void**)&g->lead_x, need * sizeof(double)));
-        RL_HIP(hipMalloc((void**)&g->lead_y, need * sizeof(double)));
+        RL_TRY(g->lead_x.reserve(need));
+        RL_TRY(g->lead_y.reserve(need));
         g->lead_cap = (size_t)nvec;
     }
     // (a child's workspace only grows: the middle frequencies take 2 nvec vectors, the two
@@ -2704,9 +2641,9 @@ static void lead_launch(rl_gridop* g, bool inverse, const double* src, double* d
     const dim3 grid((unsigned)((ncol + thr - 1) / thr)), blk(thr);
     if (inverse)
         RL_LAUNCH(k_lead_inv<N0>, grid, blk, rl_lead_inv_lds(N0), st, src, g->m0, M, ncol,
-                  RL_KCONST(g->lead_tw), dst);
+                  RL_KCONST(g->lead_tw.get()), dst);
     else
-        RL_LAUNCH(k_lead_fwd<N0>, grid, blk, 0, st, src, g->m0, M, ncol, RL_KCONST(g->lead_tw), dst);
+        RL_LAUNCH(k_lead_fwd<N0>, grid, blk, 0, st, src, g->m0, M, ncol, RL_KCONST(g->lead_tw.get()), dst);
 }
 
 static int lead_transform(rl_gridop* g, bool inverse, const double* src, double* dst, int nvec,
@@ -2786,8 +2723,8 @@ static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, doub
         const bool poly_part = form == 1 || (form == 3 && g->lr_np > 0);
         bool ready = true;
         if (poly_part)
-            ready = g->lr_part_cap >= lr_part_need(g, nvec) &&
-                    g->lr_zhat_cap >= (size_t)nvec * g->D * RL_LR_RMAX;
+            ready = g->lr_part.cap >= lr_part_need(g, nvec) &&
+                    g->lr_zhat.cap >= (size_t)nvec * g->D * RL_LR_RMAX;
         const int sNF = single ? 1 : g->sf_n, sfac = single ? 0 : g->sf_nfac;
         const int sNS = single ? (form == 2 ? g->sf_top_ns[q1] : 2) : g->sf_ns;
         if (form >= 2) ready = ready && sf_ready(g, nvec, sNF, sfac, sNS);
@@ -2824,14 +2761,8 @@ static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, doub
     if (small_try && !g->lr_dirty && g->lr_ok && g->lr_Mf_ok && nvec <= 65535) {
         const int nseg = lr_small_nseg(g->m);
         const size_t need = (size_t)nvec * g->D * nseg * RL_LR_RMAX;
-        if (g->lr_spart_cap < need && !stream_capturing(stream)) {
-            if (g->lr_spart) RL_HIP(hipFree(g->lr_spart));
-            g->lr_spart = nullptr;
-            g->lr_spart_cap = 0;
-            RL_HIP(hipMalloc((void**)&g->lr_spart, need * sizeof(double)));
-            g->lr_spart_cap = need;
-        }
-        if (g->lr_spart_cap >= need) {
+        if (g->lr_spart.cap < need && !stream_capturing(stream)) RL_TRY(g->lr_spart.reserve(need));
+        if (g->lr_spart.cap >= need) {
             trace_once("grid product: polynomial-subspace form, small batch (k_lr_small_project / k_lr_small_expand)");
             const dim3 grid(g->D * nseg, nvec), blk(RL_LR_SMALL_WG);
 #define RL_LR_SMALL(R_)                                                                           \
@@ -2926,7 +2857,7 @@ extern "C" int rl_gridop_mvm(rl_gridop* g, const double* X, double* Y, int nvec,
     if (g->lead) return lead_mvm(g, -1, X, Y, nvec, (hipStream_t)stream);
     if (g->wide) return wide_mvm(g, X, Y, nvec, (hipStream_t)stream);
     MixParams mp{g->Q, g->nfac, g->spec, g->facA, g->facW, g->facQ, g->kappa,
-                 g->mixtab_ok ? g->mixtab : nullptr,
+                 g->mixtab_ok ? g->mixtab.get() : nullptr,
                  g->mixtab_ok ? g->mixtab + (size_t)g->D * g->L : nullptr};
     return mvm_with_mix(g, mp, X, Y, nvec, (hipStream_t)stream);
 }

@@ -2,7 +2,9 @@
 // runlmc_hip.hip): rl_gridop.hip (grid operator, forms), rl_ski.hip (SKI operator products),
 // rl_solve.hip (Krylov and direct solves, host helpers, gradient partial sums).  Kernels come
 // from the rl_*.h headers; their non-template kernels have internal linkage, so that every
-// translation unit instantiates only what it launches.
+// translation unit instantiates only what it launches.  Device memory of every handle lives in
+// DevBuf members (below): a destroy function ends its streams, events and child handles and
+// deletes the handle, whose destructor frees the buffers.
 #pragma once
 #include "../../include/runlmc_hip.h"
 
@@ -132,13 +134,64 @@ struct RlKnobs {
 // (and names every hook it ignored on stderr, each once).
 RlKnobs read_knobs();
 
+// ---------------------------------------------------------------------------
+// Device memory.  Every device buffer of a handle is a DevBuf member: the handle's
+// destructor frees it, so `delete h` in a destroy function is the whole of freeing.
+// reserve() never over-allocates and keeps no contents; it knows nothing about streams,
+// so callers reserve outside a capture (the stream_capturing checks at the call sites).
+// ---------------------------------------------------------------------------
 template <class T>
-static int upload(T** dev, const std::vector<T>& host) {
-    RL_HIP(hipMalloc((void**)dev, std::max<size_t>(host.size(), 1) * sizeof(T)));
-    if (!host.empty())
-        RL_HIP(hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    return RL_OK;
-}
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;     // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p = o.p; cap = o.cap;
+            o.p = nullptr; o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    T* get() const { return p; }
+    operator T*() const { return p; }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    // at least n elements: nothing when they are there, else free and allocate exactly n
+    int reserve(size_t n) { return cap >= n ? RL_OK : alloc(n * sizeof(T), n); }
+    // exactly n elements whatever was there (contents are not kept)
+    int renew(size_t n) { return alloc(n * sizeof(T), n); }
+    // a fresh allocation holding the host array (empty input: 16 bytes / one element)
+    int upload(const T* host, size_t n) {
+        RL_TRY(alloc(std::max<size_t>(n * sizeof(T), 16), n));
+        if (n) RL_HIP(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice));
+        return RL_OK;
+    }
+    int upload(const std::vector<T>& host) {
+        RL_TRY(alloc(std::max<size_t>(host.size(), 1) * sizeof(T), host.size()));
+        if (!host.empty())
+            RL_HIP(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+        return RL_OK;
+    }
+private:
+    int alloc(size_t bytes, size_t n) {
+        reset();
+        const hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e != hipSuccess) {
+            p = nullptr;
+            return fail(RL_EHIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+        }
+        cap = n;
+        return RL_OK;
+    }
+};
 
 static const size_t kLdsSoft = 76 * 1024;    // two workgroups per CU
 static const size_t kLdsHard = 156 * 1024;   // one workgroup per CU (160 KiB LDS)
@@ -171,9 +224,8 @@ struct rl_gridop {
     // same route (gridop_create_impl: rows_too_long).
     bool wide = false;
     rl_gridop* child = nullptr;
-    double* wide_B = nullptr;   // [max_tops][D][D]
-    double* wide_Z = nullptr;   // T_q X of one top: nvec * D * m
-    size_t wide_Z_cap = 0;
+    DevBuf<double> wide_B;   // [max_tops][D][D]
+    DevBuf<double> wide_Z;   // T_q X of one top: nvec * D * m
     // 3-D grid m0 x m1 x m2 (rl_lead.h): a real transform along the leading axis (k_lead_fwd),
     // one 2-D product over (m1, m2) per leading frequency f < F = N0 / 2 + 1 -- kids[f], a
     // complete 2-D operator with D outputs holding the real rows sum_j c_q[j] cos(2 pi f j / N0)
@@ -182,15 +234,15 @@ struct rl_gridop {
     bool lead = false;
     int m0 = 0, N0 = 0;
     std::vector<rl_gridop*> kids;
-    double* lead_tw = nullptr;  // dev [N0 / 2][2]: exp(-2 pi i k / N0)
-    double *lead_x = nullptr, *lead_y = nullptr;   // [F][2][nvec][D][m1 m2] each
+    DevBuf<double> lead_tw;  // dev [N0 / 2][2]: exp(-2 pi i k / N0)
+    DevBuf<double> lead_x, lead_y;   // [F][2][nvec][D][m1 m2] each
     size_t lead_cap = 0;        // vectors they hold
     bool defer_expand = false;  // ski_mvm_int: leave the expansion to the W kernel (k_spmv_w_poly) ...
     bool expand_deferred = false;   // ... done: lr_zhat holds the mixed coefficients of the batch
     int lr_rejects = 0;         // consecutive parameter sets with a top the verification rejected
     int lr_skip = 0;            // parameter updates the verification still sits out (back-off:
                                 // 0, 1, 3 ... 31 updates after 1, 2, 3 ... rejections in a row)
-    double* lr_stat = nullptr;  // dev verdict records of the verification; lr_C lives behind them
+    DevBuf<double> lr_stat;  // dev verdict records of the verification; lr_C lives behind them
     bool lr_dirty = false;      // parameters changed since the last verification: the
                                 // set-time work (lr_setup) runs when the first batch above
                                 // the gate asks for it -- small-batch users never pay it
@@ -200,34 +252,30 @@ struct rl_gridop {
     int lr_r = 0;               // basis size in use (24 / 32 / 48)
     int lr_rank_hint = 0;       // first rank the verification tries (rl_gridop_set_rank_hint)
     size_t lr_min = 0;          // batches below this many elements stay on the FFT path
-    double* lr_beta = nullptr;  // dev [RL_LR_RMAX] recurrence coefficients
-    double* lr_nu = nullptr;    // dev [RL_LR_RMAX] normalisation
-    double* lr_phiJ = nullptr;  // dev [RL_LR_RMAX][m]
-    double* lr_C = nullptr;     // dev [max_tops][r][r]
-    double* lr_M = nullptr;     // dev [D][24][D][24]: the whole coefficient map (polynomial rounds)
+    DevBuf<double> lr_beta;  // dev [RL_LR_RMAX] recurrence coefficients
+    DevBuf<double> lr_nu;    // dev [RL_LR_RMAX] normalisation
+    DevBuf<double> lr_phiJ;  // dev [RL_LR_RMAX][m]
+    double* lr_C = nullptr;  // dev [max_tops][r][r] (inside lr_stat's allocation)
+    DevBuf<double> lr_M;     // dev [D][24][D][24]: the whole coefficient map (polynomial rounds)
     std::vector<double> lr_hC;  // host copy of lr_C for it
-    double* lr_spart = nullptr; // dev [nvec][D][nseg][r]: partial sums of k_lr_small_project
-    size_t lr_spart_cap = 0;
-    double* lr_Cx = nullptr;    // dev [RMAX][RMAX]: scratch of lr_all_coeffs
-    double* lr_Mf = nullptr;    // dev [D][r][D][r]: the coefficient map for k_lr_small_expand (any rank)
-    size_t lr_Mf_cap = 0;
+    DevBuf<double> lr_spart; // dev [nvec][D][nseg][r]: partial sums of k_lr_small_project
+    DevBuf<double> lr_Cx;    // dev [RMAX][RMAX]: scratch of lr_all_coeffs
+    DevBuf<double> lr_Mf;    // dev [D][r][D][r]: the coefficient map for k_lr_small_expand (any rank)
     bool lr_Mf_ok = false;      // ... built for the current parameters
     std::vector<double> lr_hB;  // host [Q][D][D]: the couplings lr_B holds (direct solves, rl_direct.h)
     std::vector<double> lr_hnu; // host copy of lr_nu
     unsigned long long param_ver = 0;   // bumped by every parameter update (what a factorisation was built for)
-    double* lr_B = nullptr;     // dev [max_tops][D][D]
-    double* lr_eye = nullptr;   // dev [D][D]
-    double* lr_part = nullptr;  // projection partial sums
-    size_t lr_part_cap = 0;
-    double* lr_zhat = nullptr;  // mixed coefficients [rows][r]
-    size_t lr_zhat_cap = 0;
-    double* lr_scr = nullptr;   // set-time scratch: 3 vectors of D*m + partial maxima
-    double* lr_pw = nullptr;    // the power iteration's vectors (lr_verify (iv))
-    double* lr_sel = nullptr;   // ... and the selector couplings of its groups of tops
+    DevBuf<double> lr_B;     // dev [max_tops][D][D]
+    DevBuf<double> lr_eye;   // dev [D][D]
+    DevBuf<double> lr_part;  // projection partial sums
+    DevBuf<double> lr_zhat;  // mixed coefficients [rows][r]
+    DevBuf<double> lr_scr;   // set-time scratch: 3 vectors of D*m + partial maxima
+    DevBuf<double> lr_pw;    // the power iteration's vectors (lr_verify (iv))
+    DevBuf<double> lr_sel;   // ... and the selector couplings of its groups of tops
     std::vector<double> lr_vstat;   // host [max_tops][4]: the last verification's measurements per top
                                     // (trial ratio, tail ratio, ||E v||, ||T w||: rl_gridop_form_stats)
-    double* lr_Cc = nullptr;    // dev [max_tops][r][r]: C of the polynomial tops only, contiguous
-    double* lr_Bc = nullptr;    // dev [max_tops][D][D]: their couplings (operators that mix forms)
+    DevBuf<double> lr_Cc;    // dev [max_tops][r][r]: C of the polynomial tops only, contiguous
+    DevBuf<double> lr_Bc;    // dev [max_tops][D][D]: their couplings (operators that mix forms)
     int lr_np = 0;              // polynomial tops among the Q
     // per-top forms (decided by forms_setup at every parameter update):
     //   0 transform kernels, 1 polynomial-subspace form, 2 recursive filter (rl_filter.h)
@@ -244,46 +292,44 @@ struct rl_gridop {
     int sf_ns = 2;              // states per direction the operator's filters need (2, 3 or 4)
     std::vector<int> sf_slot;   // per top: its place among the filter tops, or -1
     std::vector<int> sf_top_ns; // per top: 2, 3 or 4
-    SfTop* sf_tops = nullptr;   // dev [max_tops]
-    double* sf_pwp = nullptr;   // dev [max_tops][2 G]: the chunk states' parity weights (k_sf_carries2)
-    double* sf_blob = nullptr;  // dev: the filter part's block for k_sf_apply (rl_filter.h)
-    double* sf_blob_top = nullptr;  // dev [max_tops][...]: the same for each top alone (B = I)
-    double* sf_pw = nullptr;    // dev [max_tops][G + 1]
-    double* sf_kappa = nullptr; // dev [max_tops][D]
-    double* sf_facA = nullptr;  // dev [max_fac][D]
-    double* sf_facAW = nullptr; // dev [max_fac][D]
-    int* sf_facJ = nullptr;     // dev [max_fac]
-    double* sf_E = nullptr;     // chunk states [nchunks][rows][NF][2][NS]
-    size_t sf_E_cap = 0;
-    double* sf_Cin = nullptr;   // incoming states [nchunks][nvec][nchan][2][NS]
-    int* sf_next = nullptr;     // k_sf_apply's tile counter (zeroed by k_sf_scan)
-    size_t sf_Cin_cap = 0;
-    double* mixtab = nullptr;   // dev [D + nfac][L]: dc rows then gs rows (k_mix_tables)
+    DevBuf<SfTop> sf_tops;   // dev [max_tops]
+    DevBuf<double> sf_pwp;   // dev [max_tops][2 G]: the chunk states' parity weights (k_sf_carries2)
+    DevBuf<double> sf_blob;  // dev: the filter part's block for k_sf_apply (rl_filter.h)
+    DevBuf<double> sf_blob_top;  // dev [max_tops][...]: the same for each top alone (B = I)
+    DevBuf<double> sf_pw;    // dev [max_tops][G + 1]
+    DevBuf<double> sf_kappa; // dev [max_tops][D]
+    DevBuf<double> sf_facA;  // dev [max_fac][D]
+    DevBuf<double> sf_facAW; // dev [max_fac][D]
+    DevBuf<int> sf_facJ;     // dev [max_fac]
+    DevBuf<double> sf_E;     // chunk states [nchunks][rows][NF][2][NS]
+    DevBuf<double> sf_Cin;   // incoming states [nchunks][nvec][nchan][2][NS]
+    DevBuf<int> sf_next;     // k_sf_apply's tile counter (zeroed by k_sf_scan)
+    DevBuf<double> mixtab;   // dev [D + nfac][L]: dc rows then gs rows (k_mix_tables)
     size_t mixtab_rows = 0;     // rows allocated
     bool mixtab_ok = false;     // tables match the current parameters
     int max_tops = 0;
     FftPlan plan1, plan2;
-    cplx *tw1 = nullptr, *tw2 = nullptr, *twlo = nullptr, *twhi = nullptr;
-    int* freq1 = nullptr;
+    DevBuf<cplx> tw1, tw2, twlo, twhi;
+    DevBuf<int> freq1;
     TwiddleL twl;
     std::vector<int> h_freq1, h_freq2;
     // parameters
     int Q = 0, nfac = 0;
-    double* tops = nullptr;    // dev [max_tops][m]
-    double* spec = nullptr;    // dev [max_tops][L]
-    double* facA = nullptr;    // dev [max_fac][D]
-    double* facW = nullptr;    // dev [max_fac]
-    int* facQ = nullptr;       // dev [max_fac]
-    double* kappa = nullptr;   // dev [max_tops][D]
-    double* ones = nullptr;    // dev [D]  (identity mix for mvm_top)
+    DevBuf<double> tops;    // dev [max_tops][m]
+    DevBuf<double> spec;    // dev [max_tops][L]
+    DevBuf<double> facA;    // dev [max_fac][D]
+    DevBuf<double> facW;    // dev [max_fac]
+    DevBuf<int> facQ;       // dev [max_fac]
+    DevBuf<double> kappa;   // dev [max_tops][D]
+    DevBuf<double> ones;    // dev [D]  (identity mix for mvm_top)
     int max_fac = 0;
     // workspace: packed intermediates [pairs][D][L] complex
-    cplx* T = nullptr;
+    DevBuf<cplx> T;
     size_t T_pairs = 0;
     // a second chunk of intermediates and a side stream: consecutive chunks of a
     // large batched product run on two streams, so that one chunk's kernels fill
     // the compute units another chunk's tail leaves idle
-    cplx* T2[3] = {nullptr, nullptr, nullptr};     // workspaces of the side streams
+    DevBuf<cplx> T2[3];         // workspaces of the side streams
     size_t T2_pairs = 0;
     int nside = 0;              // side streams prepared (product runs on 1 + nside streams)
     cplx* Tcur = nullptr;       // workspace of the chunk being launched
@@ -295,8 +341,8 @@ struct rl_gridop {
     // of a pair fit one LDS tile
     bool v1p = false;
     FftPlan planL;
-    cplx* twL = nullptr;       // exp(-2 pi i k / L)
-    double* spec1 = nullptr;   // dev [max_tops][L], scrambled order of the single-level transform
+    DevBuf<cplx> twL;       // exp(-2 pi i k / L)
+    DevBuf<double> spec1;   // dev [max_tops][L], scrambled order of the single-level transform
     size_t lds1 = 0;
     int thr1 = 256;
     int v1p_min = 64;          // vectors from which the single-tile product is used
@@ -310,10 +356,10 @@ struct rl_gridop {
 struct SkiTerm {
     rl_gridop* g = nullptr;
     int ngrid = 0;
-    int *W_indptr = nullptr, *W_indices = nullptr;
-    double* W_data = nullptr;
-    int *WT_indptr = nullptr, *WT_indices = nullptr;
-    double* WT_data = nullptr;
+    DevBuf<int> W_indptr, W_indices;
+    DevBuf<double> W_data;
+    DevBuf<int> WT_indptr, WT_indices;
+    DevBuf<double> WT_data;
     int nnzWT = 0;
     // Interpolation structure, when W has it (every row at most 4 entries in
     // consecutive columns, rows sorted by first column -- cubic interpolation of
@@ -321,9 +367,9 @@ struct SkiTerm {
     // that the data rows of every grid row are one CONSECUTIVE range starting
     // at WT_lo[r] (zero weights kept).  Both remove one level of dependent
     // loads from the fused products of the small-batch solver.
-    int* W4_base = nullptr;
-    double* W4_w = nullptr;
-    int* WT_lo = nullptr;
+    DevBuf<int> W4_base;
+    DevBuf<double> W4_w;
+    DevBuf<int> WT_lo;
     // largest data range / entry count of any RL_THREADS consecutive grid rows
     // (k_spmv_wt_staged stages them in LDS); 0 = no structure
     int wt_xmax = 0, wt_emax = 0;
@@ -345,31 +391,26 @@ struct PcState {
     double logdet = 0.0, cond = 0.0;    // log det P; squared pivot ratio of chol(G)
     std::vector<int> h_piv;             // host [k]
     std::vector<double> h_pivval;       // host [k]
-    double* L = nullptr;                // dev [kp][n]
-    size_t L_cap = 0;
-    double *d = nullptr, *row = nullptr, *e = nullptr;   // dev [n]: residual diagonal, K e_p, one-hot vector
-    int* mark = nullptr;                // dev [n]: 1 on rows that were pivots
-    int* piv = nullptr;                 // dev [RL_PC_MAXRANK]
-    double* pivval = nullptr;           // dev [RL_PC_MAXRANK + 1]: d at the pivots, then max d^(0)
-    double* pv = nullptr;               // dev [RL_PC_NBLK]: arg-max partials
-    int* pi = nullptr;
-    double *inv = nullptr, *isq = nullptr, *sq = nullptr;   // dev [n]: 1 / eps, 1 / sqrt(eps), sqrt(eps)
+    DevBuf<double> L;                // dev [kp][n]
+    DevBuf<double> d, row, e;   // dev [n]: residual diagonal, K e_p, one-hot vector
+    DevBuf<int> mark;                // dev [n]: 1 on rows that were pivots
+    DevBuf<int> piv;                 // dev [RL_PC_MAXRANK]
+    DevBuf<double> pivval;           // dev [RL_PC_MAXRANK + 1]: d at the pivots, then max d^(0)
+    DevBuf<double> pv;               // dev [RL_PC_NBLK]: arg-max partials
+    DevBuf<int> pi;
+    DevBuf<double> inv, isq, sq;   // dev [n]: 1 / eps, 1 / sqrt(eps), sqrt(eps)
     unsigned long long eps_ver = ~0ull;
     double sum_log_eps = 0.0;
-    double *Mt = nullptr, *Mst = nullptr;   // dev [kp][kp]: -G^-1 and the sample map, transposed
+    DevBuf<double> Mt, Mst;   // dev [kp][kp]: -G^-1 and the sample map, transposed
     bool sample_ok = false;
-    double* part = nullptr;             // dev [chunks][nvp][kp]: k_pc_project's partial sums
-    size_t part_cap = 0;
-    double* cT = nullptr;               // dev [kp][nvp]
-    size_t cT_cap = 0;
-    std::vector<double*> tops;          // dev, per term: top rows [Q][m] where the grid keeps none
-    std::vector<size_t> tops_cap;
-    std::vector<double*> B;             // dev, per term: couplings [Q][D][D]
-    std::vector<size_t> B_cap;
+    DevBuf<double> part;             // dev [chunks][nvp][kp]: k_pc_project's partial sums
+    DevBuf<double> cT;               // dev [kp][nvp]
+    std::vector<DevBuf<double>> tops;   // dev, per term: top rows [Q][m] where the grid keeps none
+    std::vector<DevBuf<double>> B;      // dev, per term: couplings [Q][D][D]
     double build_ms[4] = {0, 0, 0, 0};  // last build: diagonal / products / step kernels / Gram + host
 };
 
-// buffers of one rl_solve_batch call
+// buffers of one rl_solve_batch call: a plain view of pointers, copied into launch closures
 struct SolverWork {
     double* vec[10] = {nullptr, nullptr, nullptr, nullptr, nullptr,
                        nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -378,54 +419,55 @@ struct SolverWork {
     double* part[4] = {nullptr, nullptr, nullptr, nullptr};
     int* count = nullptr;   // [0] active systems, [1] global iteration counter, [2] done blocks
     double* resid = nullptr; // [nrhs] explicit residual norms
-    double* lanczos = nullptr;
+    double* lanczos = nullptr;  // rl_ski::lanczos_buf
+};
+// ... and their owner: a solve's local (rl_solve.hip SolverWorkGuard), or the handle between solves
+struct SolverBufs {
+    DevBuf<double> vec[10], S[2], part[4], resid;
+    DevBuf<int> I, count;
+    SolverWork view() const {
+        SolverWork w;
+        for (int i = 0; i < 10; ++i) w.vec[i] = vec[i];
+        for (int i = 0; i < 2; ++i) w.S[i] = S[i];
+        for (int i = 0; i < 4; ++i) w.part[i] = part[i];
+        w.I = I; w.count = count; w.resid = resid;
+        return w;
+    }
 };
 
 struct rl_ski {
     RlKnobs kn;         // environment switches as they were when the handle was created
     // Lanczos coefficients of a solve: kept between calls (a hipMalloc / hipFree
     // pair per solve costs ~200 us, as much as four C2 solver rounds)
-    double* lanczos_buf = nullptr;
-    size_t lanczos_bytes = 0;
+    DevBuf<double> lanczos_buf;
     int device = 0;     // copy of g->device: the grid operator may be gone at destroy time
-    std::vector<SkiTerm> extra;   // terms beyond the first (rl_ski_add_term)
+    std::vector<SkiTerm> terms;   // terms[0]: the term of rl_ski_create, on g; then rl_ski_add_term's
     int max_ngrid = 0;
     rl_gridop* g = nullptr;
-    int n = 0, ngrid = 0, nnz = 0, nnzWT = 0;
-    int *W4_base = nullptr, *WT_lo = nullptr;     // interpolation structure (SkiTerm)
-    int wt_xmax = 0, wt_emax = 0, w_xmax = 0;
-    double* W4_w = nullptr;
-    int *W_indptr = nullptr, *W_indices = nullptr;
-    double* W_data = nullptr;
-    int *WT_indptr = nullptr, *WT_indices = nullptr;
-    double* WT_data = nullptr;
-    double* noise_diag = nullptr;   // dev [n]
+    int n = 0, ngrid = 0, nnz = 0;
+    DevBuf<double> noise_diag;   // dev [n]
     bool has_noise = false;
-    double *G1 = nullptr, *G2 = nullptr;   // dev [cap][D*m] grid-side temporaries
+    DevBuf<double> G1, G2;   // dev [cap][D*m] grid-side temporaries
     int cap = 0;
     // Internal row order: data points sorted by grid position (W, WT and
     // noise_diag above are stored in THAT order); perm[i] = caller's row of
     // internal row i.  P1/P2: dev [pcap][n] staging for caller-order entry points.
     // polynomial rounds of small solves (rl_solver.h, Minres2Bufs::poly_part): row
     // blocks that lie inside one output, first block of each output, partial sums
-    std::vector<int> h_base;
-    int *poly_tab = nullptr, *poly_ob = nullptr;
+    DevBuf<int> poly_tab, poly_ob;
     int poly_nblk = 0;              // 0: not built yet, -1: not applicable
-    double* poly_part = nullptr;
-    size_t poly_part_cap = 0;
+    DevBuf<double> poly_part;
     // row-polynomial form of large solver rounds (rl_rowpoly.h): F = W Phi, built per rank
-    double* rp_F = nullptr;
+    DevBuf<double> rp_F;
     int rp_R = 0;                   // rank F was built for (0: none)
-    double* rp_Fc = nullptr;        // the same in the CALLER's row order (rl_ski_mvm: no row permutations)
+    DevBuf<double> rp_Fc;        // the same in the CALLER's row order (rl_ski_mvm: no row permutations)
     int rp_Fc_R = 0;
-    int* rp_base_c = nullptr;       // interpolation entries in the caller's row order (FLY kernels)
-    double* rp_w4_c = nullptr;
-    int *rp_runs = nullptr, *rp_run_ptr = nullptr, *rp_out_end = nullptr;
+    DevBuf<int> rp_base_c;       // interpolation entries in the caller's row order (FLY kernels)
+    DevBuf<double> rp_w4_c;
+    DevBuf<int> rp_runs, rp_run_ptr, rp_out_end;
     int rp_nruns = 0;
-    double* rp_part = nullptr;
-    size_t rp_part_cap = 0;
-    double* rp_nrm = nullptr;       // fused B: [nrhs] coefficients + [nrhs][rp_nruns] partial norms
-    size_t rp_nrm_cap = 0;
+    DevBuf<double> rp_part;
+    DevBuf<double> rp_nrm;       // fused B: [nrhs] coefficients + [nrhs][rp_nruns] partial norms
     RpFuse rp_fuse{nullptr, nullptr, nullptr};   // set by the solver around ONE operator product
     // MINRES's P inside the expansion (rl_rowpoly.h RpPFuse): set by the solver around ONE
     // operator product together with rp_mid, which launches P's scalar head between the
@@ -433,12 +475,11 @@ struct rl_ski {
     // three arrays of [nrhs][ceil(n / 256)] partial sums
     RpPFuse rp_pfuse{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     std::function<void(hipStream_t)> rp_mid;
-    double* rp_pp = nullptr;
-    size_t rp_pp_cap = 0;
+    DevBuf<double> rp_pp;
     std::vector<int> eps_end;       // noise in runs: rows [eps_end[k-1], eps_end[k]) carry eps_val[k]
     std::vector<double> eps_val;    // (empty: more than RL_MAX_D runs)
     bool permuted = false;
-    int* perm = nullptr;
+    DevBuf<int> perm;
     std::vector<int> h_perm;
     // rl_ski_mvm's row-polynomial form in the CALLER's row order reuses the runs, the output
     // borders and the noise array of the SORTED order: valid only when every output's rows
@@ -446,7 +487,7 @@ struct rl_ski {
     // the noise array reads the same in both (rl_ski_set_noise).  -1: not checked yet
     int caller_ranges_same = -1;
     bool caller_noise_same = true;
-    double *P1 = nullptr, *P2 = nullptr;
+    DevBuf<double> P1, P2;
     int pcap = 0;
     hipStream_t solver_stream = nullptr;   // capturable stream of rl_solve_batch
     int* pin_count = nullptr;              // pinned host [2]: active-system counts in flight
@@ -454,7 +495,7 @@ struct rl_ski {
     // the solver's buffers are kept between calls (a solve frees eighteen of them
     // and a hipFree is ~100 us: 1.7 of the 2.9 ms a C2 solve spent outside its
     // rounds); capacities in elements.  RUNLMC_WS_CACHE_MB bounds what is kept.
-    SolverWork ws;
+    SolverBufs ws;
     bool ws_valid = false;
     size_t ws_vec_cap = 0, ws_rhs_cap = 0, ws_part_cap = 0;
     // direct solves through the polynomial form (rl_direct.h): K~ = F M F^T + E
@@ -463,9 +504,8 @@ struct rl_ski {
     std::vector<int> h_run_ptr, h_out_end;   // host copies of rp_run_ptr / rp_out_end
     std::vector<double> dz_U;           // host [D][r][r]: F_d^T F_d on the unnormalised q_j, per (handle, rank)
     int dz_U_R = 0;
-    double* dz_Zt = nullptr;            // dev [D r][D r]: the solve map, scalings folded in
-    size_t dz_Zt_cap = 0;
-    double* dz_inv = nullptr;           // dev [n]: 1 / eps per row
+    DevBuf<double> dz_Zt;            // dev [D r][D r]: the solve map, scalings folded in
+    DevBuf<double> dz_inv;           // dev [n]: 1 / eps per row
     std::vector<double> dz_eps;         // host [D]: the noise level of each output ...
     const char* dz_eps_why = nullptr;   // ... or why there is none (not constant per output, not positive)
     unsigned long long dz_eps_ver = ~0ull;   // noise_ver those (and dz_inv) were derived from
@@ -475,23 +515,20 @@ struct rl_ski {
     const char* dz_fail_why = nullptr;  // "not available" decided for the versions below (not recomputed per solve)
     unsigned long long dz_fail_param_ver = 0, dz_fail_noise_ver = 0;
     int dz_fail_streak = 0, dz_fail_skip = 0;   // back-off of the attempts after failures in a row
-    double *dz_p = nullptr, *dz_q = nullptr;       // dev [cap][n]: PCG's direction and operator product
+    DevBuf<double> dz_p, dz_q;       // dev [cap][n]: PCG's direction and operator product
     size_t dz_pq_cap = 0;
-    double* dz_scal = nullptr;          // dev [dz_scal_cap][2]: PCG's (rho, rho_prev)
-    size_t dz_scal_cap = 0;             // (its own: rl_solve_direct grows dz_part / dz_go without it)
+    DevBuf<double> dz_scal;          // dev [cap][2]: PCG's (rho, rho_prev); a capacity of
+                                     // its own (rl_solve_direct grows dz_part / dz_go without it)
     unsigned long long dz_param_ver = 0, dz_noise_ver = 0;
     int dz_R = 0;
     // the 96-function preconditioner of an operator without a polynomial row (rl_solve.hip: hz_*)
     bool dz_want_sample = false;        // rl_ski_precond_sample was called: factorisations keep the square-root map
-    double* dz_Zh = nullptr;            // dev [D r][D r]: that map, transposed (rl_solve.hip dz_host_map)
-    size_t dz_Zh_cap = 0;
+    DevBuf<double> dz_Zh;            // dev [D r][D r]: that map, transposed (rl_solve.hip dz_host_map)
     bool dz_Zh_valid = false;
-    double* dz_isq = nullptr;           // dev [n]: 1 / sqrt(eps) per row
+    DevBuf<double> dz_isq;           // dev [n]: 1 / sqrt(eps) per row
     unsigned long long dz_isq_ver = ~0ull;
-    double* dz_smp = nullptr;           // dev [cap][n]: scaled probes
-    size_t dz_smp_cap = 0;
-    double* dz_rec = nullptr;           // dev [cap][nrhs][2]: conjugate gradients' scalars of a recorded run
-    size_t dz_rec_cap = 0;
+    DevBuf<double> dz_smp;           // dev [cap][n]: scaled probes
+    DevBuf<double> dz_rec;           // dev [cap][nrhs][2]: conjugate gradients' scalars of a recorded run
     bool dz_hz = false;                 // the valid factorisation is THAT one (dz_Zt: [D 96][D 96])
     int hz_R = 0;                       // its basis size (blocks of 48; "96" below stands for it)
     bool hz_traced = false;
@@ -499,28 +536,30 @@ struct rl_ski {
     bool hz_basis_tried = false;        // basis generated (or found unusable) once per handle
     const char* hz_why = nullptr;       // why the handle has none (decided once)
     std::vector<double> hz_hnu;         // host [96]: normalisation of the basis
-    double* hz_beta = nullptr;          // dev [96]: recurrence coefficients
-    double* hz_phi = nullptr;           // dev [96 rounded up to D][m]: the functions on the grid
-    double* hz_tphi = nullptr;          // dev, same size: a top row applied to them
-    double* hz_C = nullptr;             // dev [96][96]
-    double* hz_F = nullptr;             // dev [96][n]: F = W Phi, unnormalised, degree-major
-    double* hz_ones = nullptr;          // dev [n]
+    DevBuf<double> hz_beta;          // dev [96]: recurrence coefficients
+    DevBuf<double> hz_phi;           // dev [96 rounded up to D][m]: the functions on the grid
+    DevBuf<double> hz_tphi;          // dev, same size: a top row applied to them
+    DevBuf<double> hz_C;             // dev [96][96]
+    DevBuf<double> hz_F;             // dev [96][n]: F = W Phi, unnormalised, degree-major
+    DevBuf<double> hz_ones;          // dev [n]
     std::vector<double> hz_U;           // host [D][96][96]: F_d^T F_d, once per handle
-    double* hz_part = nullptr;          // dev [2][runs][cap][48]
-    double* hz_zhat = nullptr;          // dev [2][cap][D][48]
-    double* hz_tmp = nullptr;           // dev [cap][n]: the first half's expansion
-    double* hz_S = nullptr;             // dev [cap][D R]: projections summed over the runs
-    double* hz_P = nullptr;             // dev [RL_HZ_FS][cap][D R]: the map's partial products
+    DevBuf<double> hz_part;          // dev [2][runs][cap][48]
+    DevBuf<double> hz_zhat;          // dev [2][cap][D][48]
+    DevBuf<double> hz_tmp;           // dev [cap][n]: the first half's expansion
+    DevBuf<double> hz_S;             // dev [cap][D R]: projections summed over the runs
+    DevBuf<double> hz_P;             // dev [RL_HZ_FS][cap][D R]: the map's partial products
     size_t hz_vec_cap = 0;
     double dz_logdet = 0.0;             // log det K~ of that factorisation
     double dz_cond = 0.0;               // ratio of the largest to the smallest pivot of chol(S), squared
-    double *dz_res = nullptr, *dz_cor = nullptr;   // dev [cap][n]: residuals, corrections
+    DevBuf<double> dz_res, dz_cor;   // dev [cap][n]: residuals, corrections
     size_t dz_vec_cap = 0;
-    double* dz_part = nullptr;          // dev [cap][RL_DZ_NBLK] partial sums, then [cap] norms
-    int* dz_go = nullptr;               // dev [cap]: systems still being refined
+    DevBuf<double> dz_part;          // dev [cap][RL_DZ_NBLK] partial sums, then [cap] norms
+    DevBuf<int> dz_go;               // dev [cap]: systems still being refined
     size_t dz_rhs_cap = 0;
     PcState pc;                         // the pivoted-Cholesky preconditioner (rl_ski_set_pivchol)
 };
+
+inline bool single_term(const rl_ski* s) { return s->terms.size() == 1; }
 
 // destroys a half-built handle on every early return of a create function
 template <class H, int (*Destroy)(H*)>
@@ -550,7 +589,6 @@ int mvm_chunk_v2(rl_gridop* g, const MixParams& mp, const double* Xc, double* Yc
 int mvm_chunk_v1(rl_gridop* g, const MixParams& mp, const double* Xc, double* Yc, int nv, size_t pairs,
                  hipStream_t stream, const Gather* gather = nullptr, int* bump = nullptr);
 // rl_ski.hip
-int upload_raw(void** dev, const void* host, size_t bytes);
 int ski_reserve(rl_ski* s, int nvec);
 int ski_wt_int(rl_ski* s, const double* Xp, double* G, int nvec, hipStream_t st, int* bump = nullptr);
 int ski_reserve_perm(rl_ski* s, int nvec);
@@ -561,6 +599,4 @@ int rp_prepare(rl_ski* s, int nvec);
 bool rp_ready(const rl_ski* s, int nvec);
 int ski_mvm_int(rl_ski* s, const double* Xp, double* Yp, int nvec, hipStream_t st,
                 int* bump = nullptr, bool noise = true);
-// rl_solve.hip
-void free_work(SolverWork& w);
 

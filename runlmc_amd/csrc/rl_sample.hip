@@ -24,35 +24,30 @@ struct rl_sampler {
     bool one_launch = false;
     int cols = 1, rows = 1, K1 = 0;
     FftPlan plan1, plan2;
-    cplx *tw1 = nullptr, *tw2 = nullptr, *twlo = nullptr;
-    int *freq1 = nullptr, *pos1 = nullptr, *freq2 = nullptr;
-    int* eC = nullptr;           // [nemb]
-    int* efoff = nullptr;
-    long long* ezoff = nullptr;
-    double* F = nullptr;         // all blocks
-    double* slam = nullptr;      // [nemb][Ltot]
+    DevBuf<cplx> tw1, tw2, twlo;
+    DevBuf<int> freq1, pos1, freq2;
+    DevBuf<int> eC;           // [nemb]
+    DevBuf<int> efoff;
+    DevBuf<long long> ezoff;
+    DevBuf<double> F;         // all blocks
+    DevBuf<double> slam;      // [nemb][Ltot]
     std::vector<double> h_lam;   // host [nemb][Ltot]: the clipped spectra (rl_sampler_spectrum_host)
     std::vector<int> emb_of;     // per row: its place among the embedding rows, or -1
-    cplx* T = nullptr;           // [pairs][D][Ltot]
+    DevBuf<cplx> T;           // [pairs][D][Ltot]
     size_t T_pairs = 0;
     // polynomial rows
-    int* pC = nullptr;
-    int* pfoff = nullptr;
-    long long* pzoff = nullptr;
-    double* G = nullptr;         // [npoly][r][r]
-    double* zhat = nullptr;      // [nsamp][D][r]
-    size_t zhat_cap = 0;
+    DevBuf<int> pC;
+    DevBuf<int> pfoff;
+    DevBuf<long long> pzoff;
+    DevBuf<double> G;         // [npoly][r][r]
+    DevBuf<double> zhat;      // [nsamp][D][r]
 };
 
 static void smp_free_params(rl_sampler* h) {
-    void* ptrs[] = {h->tw1, h->tw2, h->twlo, h->freq1, h->pos1, h->freq2, h->eC, h->efoff, h->ezoff,
-                    h->F, h->slam, h->pC, h->pfoff, h->pzoff, h->G};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    h->tw1 = h->tw2 = h->twlo = nullptr;
-    h->freq1 = h->pos1 = h->freq2 = h->eC = h->efoff = h->pC = h->pfoff = nullptr;
-    h->ezoff = h->pzoff = nullptr;
-    h->F = h->slam = h->G = nullptr;
+    for (DevBuf<cplx>* b : {&h->tw1, &h->tw2, &h->twlo}) b->reset();
+    for (DevBuf<int>* b : {&h->freq1, &h->pos1, &h->freq2, &h->eC, &h->efoff, &h->pC, &h->pfoff}) b->reset();
+    for (DevBuf<long long>* b : {&h->ezoff, &h->pzoff}) b->reset();
+    for (DevBuf<double>* b : {&h->F, &h->slam, &h->G}) b->reset();
     h->set = false;
 }
 
@@ -209,9 +204,6 @@ static std::vector<double> smp_spectrum(const double* ext, int n1, int n2) {
 extern "C" int rl_sampler_destroy(rl_sampler* h) {
     if (!h) return RL_OK;
     (void)hipSetDevice(h->device);
-    smp_free_params(h);
-    if (h->T) (void)hipFree(h->T);
-    if (h->zhat) (void)hipFree(h->zhat);
     delete h;
     return RL_OK;
 }
@@ -299,11 +291,11 @@ extern "C" int rl_sampler_set(rl_sampler* h, int Q, const int* nchan, const doub
     for (int q = 0, e = 0; q < Q; ++q)
         if (forms[q] == 0) h->emb_of[q] = e++;
     std::vector<double> hF(F, F + fo);
-    RL_TRY(upload(&h->F, hF));
+    RL_TRY(h->F.upload(hF));
     if (nemb) {
-        RL_TRY(upload(&h->eC, eC));
-        RL_TRY(upload(&h->efoff, efoff));
-        RL_TRY(upload(&h->ezoff, ezoff));
+        RL_TRY(h->eC.upload(eC));
+        RL_TRY(h->efoff.upload(efoff));
+        RL_TRY(h->ezoff.upload(ezoff));
         // spectra
         const int n1 = N1s, n2 = twod ? N2s : 1;
         const size_t ext_len = (size_t)(n1 / 2 + 1) * (twod ? n2 / 2 + 1 : 1);
@@ -327,7 +319,7 @@ extern "C" int rl_sampler_set(rl_sampler* h, int Q, const int* nchan, const doub
             if (clipped) clipped[q] = tot > 0.0L ? (double)(neg / tot) : 0.0;
             ++e;
         }
-        RL_TRY(upload(&h->slam, slam));
+        RL_TRY(h->slam.upload(slam));
         // transform layout
         h->one_launch = !twod && Ltot <= RL_SAMPLER_LDS_MAX;
         if (h->one_launch) {
@@ -352,14 +344,14 @@ extern "C" int rl_sampler_set(rl_sampler* h, int Q, const int* nchan, const doub
         }
         h->plan1 = smp_plan(h->N1);
         const std::vector<int> f1 = smp_pos_to_freq(h->plan1);
-        RL_TRY(upload(&h->freq1, f1));
-        RL_TRY(upload(&h->pos1, smp_invert(f1)));
-        RL_TRY(upload(&h->tw1, smp_unity(h->N1, 1, h->N1)));
+        RL_TRY(h->freq1.upload(f1));
+        RL_TRY(h->pos1.upload(smp_invert(f1)));
+        RL_TRY(h->tw1.upload(smp_unity(h->N1, 1, h->N1)));
         if (!h->one_launch) {
             h->plan2 = smp_plan(h->N2);
-            RL_TRY(upload(&h->freq2, smp_pos_to_freq(h->plan2)));
-            RL_TRY(upload(&h->tw2, smp_unity(h->N2, 1, h->N2)));
-            RL_TRY(upload(&h->twlo, smp_unity(h->N2, 1, Ltot)));
+            RL_TRY(h->freq2.upload(smp_pos_to_freq(h->plan2)));
+            RL_TRY(h->tw2.upload(smp_unity(h->N2, 1, h->N2)));
+            RL_TRY(h->twlo.upload(smp_unity(h->N2, 1, Ltot)));
             h->cols = std::max(1, std::min(16, kSmpTile / h->N1));
             h->rows = std::max(1, std::min(16, kSmpTile / h->N2));
             while (h->rows > 1 && (long long)h->N2 * (h->rows | 1) > kSmpTile) --h->rows;
@@ -367,11 +359,11 @@ extern "C" int rl_sampler_set(rl_sampler* h, int Q, const int* nchan, const doub
         }
     }
     if (npoly) {
-        RL_TRY(upload(&h->pC, pC));
-        RL_TRY(upload(&h->pfoff, pfoff));
-        RL_TRY(upload(&h->pzoff, pzoff));
+        RL_TRY(h->pC.upload(pC));
+        RL_TRY(h->pfoff.upload(pfoff));
+        RL_TRY(h->pzoff.upload(pzoff));
         std::vector<double> hG(poly_sqrt, poly_sqrt + (size_t)npoly * poly_rank * poly_rank);
-        RL_TRY(upload(&h->G, hG));
+        RL_TRY(h->G.upload(hG));
     }
     *zlen = h->zlen;
     h->set = true;
@@ -416,10 +408,8 @@ extern "C" int rl_sampler_draw(rl_sampler* h, const double* Z, double* U, int ns
             trace_once("function draws: embedding, two passes (k_smp_cols / k_smp_rows)");
             const size_t Ltot = (size_t)h->N1 * h->N2;
             if ((size_t)npairs > h->T_pairs) {
-                if (h->T) RL_HIP(hipFree(h->T));
-                h->T = nullptr;
                 h->T_pairs = 0;
-                if (hipMalloc((void**)&h->T, (size_t)npairs * D * Ltot * sizeof(cplx)) != hipSuccess) {
+                if (h->T.renew((size_t)npairs * D * Ltot) != RL_OK) {
                     (void)hipGetLastError();
                     return fail(RL_ENOMEM, "rl_sampler_draw: no device memory for the intermediates of " +
                                                std::to_string(npairs) + " pairs");
@@ -442,13 +432,7 @@ extern "C" int rl_sampler_draw(rl_sampler* h, const double* Z, double* U, int ns
         if (!h->g->lr_beta || h->g->lr_r != r)
             return fail(RL_EINVAL, "rl_sampler_draw: the grid operator's polynomial form changed since rl_sampler_set");
         const size_t need = (size_t)nsamp * D * r;
-        if (need > h->zhat_cap) {
-            if (h->zhat) RL_HIP(hipFree(h->zhat));
-            h->zhat = nullptr;
-            h->zhat_cap = 0;
-            RL_HIP(hipMalloc((void**)&h->zhat, need * sizeof(double)));
-            h->zhat_cap = need;
-        }
+        RL_TRY(h->zhat.reserve(need));
         trace_once("function draws: polynomial rows (k_smp_poly_coef + k_lr_expand)");
         RL_LAUNCH(k_smp_poly_coef, dim3((unsigned)((need + 255) / 256)), dim3(RL_SMP_THREADS), 0, st, Z, h->zlen,
                   h->npoly, (const int*)h->pC, (const int*)h->pfoff, (const long long*)h->pzoff,

@@ -43,12 +43,6 @@ static int check_csr(const int* indptr, const int* indices, int nrows, int ncols
     return RL_OK;
 }
 
-int upload_raw(void** dev, const void* host, size_t bytes) {
-    RL_HIP(hipMalloc(dev, std::max<size_t>(bytes, 16)));
-    if (bytes) RL_HIP(hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice));
-    return RL_OK;
-}
-
 // Upload one term's CSR pair, rows of W (and column indices of WT) renumbered
 // by `perm` (perm[i] = caller's row of internal row i) when given.
 static int upload_term(SkiTerm* t, int n, int ngrid, const int* W_indptr, const int* W_indices,
@@ -124,9 +118,9 @@ static int upload_term(SkiTerm* t, int n, int ngrid, const int* W_indptr, const 
                 }
             }
             t->h_base = base;
-            RL_TRY(upload_raw((void**)&t->W4_base, base.data(), (size_t)n * sizeof(int)));
-            RL_TRY(upload_raw((void**)&t->W4_w, w4.data(), (size_t)4 * n * sizeof(double)));
-            RL_TRY(upload_raw((void**)&t->WT_lo, lo.data(), (size_t)ngrid * sizeof(int)));
+            RL_TRY(t->W4_base.upload(base.data(), (size_t)n));
+            RL_TRY(t->W4_w.upload(w4.data(), (size_t)4 * n));
+            RL_TRY(t->WT_lo.upload(lo.data(), (size_t)ngrid));
             WT_indptr = sp_ptr.data(); WT_indices = sp_idx.data(); WT_data = sp_val.data();
             for (int r0 = 0; r0 < n; r0 += RL_THREADS)
                 t->w_xmax = std::max(t->w_xmax,
@@ -141,12 +135,12 @@ static int upload_term(SkiTerm* t, int n, int ngrid, const int* W_indptr, const 
     }
     const size_t nnzT = WT_indptr[ngrid];
     t->nnzWT = (int)nnzT;
-    RL_TRY(upload_raw((void**)&t->W_indptr, W_indptr, (size_t)(n + 1) * sizeof(int)));
-    RL_TRY(upload_raw((void**)&t->W_indices, W_indices, nnz * sizeof(int)));
-    RL_TRY(upload_raw((void**)&t->W_data, W_data, nnz * sizeof(double)));
-    RL_TRY(upload_raw((void**)&t->WT_indptr, WT_indptr, (size_t)(ngrid + 1) * sizeof(int)));
-    RL_TRY(upload_raw((void**)&t->WT_indices, WT_indices, nnzT * sizeof(int)));
-    RL_TRY(upload_raw((void**)&t->WT_data, WT_data, nnzT * sizeof(double)));
+    RL_TRY(t->W_indptr.upload(W_indptr, (size_t)n + 1));
+    RL_TRY(t->W_indices.upload(W_indices, nnz));
+    RL_TRY(t->W_data.upload(W_data, nnz));
+    RL_TRY(t->WT_indptr.upload(WT_indptr, (size_t)ngrid + 1));
+    RL_TRY(t->WT_indices.upload(WT_indices, nnzT));
+    RL_TRY(t->WT_data.upload(WT_data, nnzT));
     return RL_OK;
 }
 
@@ -183,19 +177,16 @@ extern "C" int rl_ski_create(rl_gridop* g, int n, const int* W_indptr, const int
     if (!identity) {
         s->permuted = true;
         s->h_perm = perm;
-        RL_TRY(upload_raw((void**)&s->perm, perm.data(), (size_t)n * sizeof(int)));
+        RL_TRY(s->perm.upload(perm.data(), (size_t)n));
     }
     SkiTerm t0;
+    t0.g = g;
     RL_TRY(upload_term(&t0, n, ngrid, W_indptr, W_indices, W_data, WT_indptr, WT_indices,
                        WT_data, s->permuted ? &s->h_perm : nullptr));
-    s->W_indptr = t0.W_indptr; s->W_indices = t0.W_indices; s->W_data = t0.W_data;
-    s->WT_indptr = t0.WT_indptr; s->WT_indices = t0.WT_indices; s->WT_data = t0.WT_data;
-    s->W4_base = t0.W4_base; s->W4_w = t0.W4_w; s->WT_lo = t0.WT_lo; s->nnzWT = t0.nnzWT;
-    s->h_base.swap(t0.h_base);
-    s->wt_xmax = t0.wt_xmax; s->wt_emax = t0.wt_emax; s->w_xmax = t0.w_xmax;
+    s->terms.push_back(std::move(t0));
     s->max_ngrid = ngrid;
     s->nnz = W_indptr[n];
-    RL_HIP(hipMalloc((void**)&s->noise_diag, (size_t)n * sizeof(double)));
+    RL_TRY(s->noise_diag.reserve((size_t)n));
     RL_HIP(hipMemset(s->noise_diag, 0, (size_t)n * sizeof(double)));
     *out = guard.release();
     return RL_OK;
@@ -217,10 +208,9 @@ extern "C" int rl_ski_add_term(rl_ski* s, rl_gridop* g, const int* W_indptr,
     SkiTerm t;
     t.g = g;
     // the handle's row order was fixed by its first term
-    int rc = upload_term(&t, s->n, ngrid, W_indptr, W_indices, W_data, WT_indptr, WT_indices,
-                         WT_data, s->permuted ? &s->h_perm : nullptr);
-    s->extra.push_back(t);     // pushed even on failure so destroy frees what was uploaded
-    if (rc != RL_OK) return rc;
+    RL_TRY(upload_term(&t, s->n, ngrid, W_indptr, W_indices, W_data, WT_indptr, WT_indices,
+                       WT_data, s->permuted ? &s->h_perm : nullptr));
+    s->terms.push_back(std::move(t));
     if (ngrid > s->max_ngrid) {
         s->max_ngrid = ngrid;
         s->cap = 0;            // grid-side temporaries must grow
@@ -232,37 +222,10 @@ extern "C" int rl_ski_add_term(rl_ski* s, rl_gridop* g, const int* W_indptr,
 extern "C" int rl_ski_destroy(rl_ski* s) {
     if (!s) return RL_OK;
     (void)hipSetDevice(s->device);
-    for (SkiTerm& t : s->extra) {
-        void* tp[] = {t.W_indptr, t.W_indices, t.W_data, t.WT_indptr, t.WT_indices, t.WT_data,
-                      t.W4_base, t.W4_w, t.WT_lo};
-        for (void* p : tp)
-            if (p) (void)hipFree(p);
-    }
     if (s->solver_stream) (void)hipStreamDestroy(s->solver_stream);
     if (s->pin_count) (void)hipHostFree(s->pin_count);
     for (hipEvent_t e : s->count_ev)
         if (e) (void)hipEventDestroy(e);
-    if (s->ws_valid) free_work(s->ws);
-    void* ptrs[] = {s->W_indptr, s->W_indices, s->W_data, s->WT_indptr, s->WT_indices,
-                    s->WT_data, s->noise_diag, s->G1, s->G2, s->perm, s->P1, s->P2,
-                    s->W4_base, s->W4_w, s->WT_lo, s->lanczos_buf, s->poly_tab, s->poly_ob,
-                    s->poly_part, s->rp_F, s->rp_Fc, s->rp_runs, s->rp_run_ptr, s->rp_out_end, s->rp_part, s->rp_nrm, s->rp_pp,
-                    s->rp_base_c, s->rp_w4_c, s->dz_Zt, s->dz_inv, s->dz_res, s->dz_cor, s->dz_part,
-                    s->dz_go, s->dz_p, s->dz_q, s->dz_scal, s->hz_beta, s->hz_phi, s->hz_tphi, s->hz_C,
-                    s->hz_F, s->hz_ones, s->hz_part, s->hz_zhat, s->hz_tmp, s->hz_S, s->hz_P, s->dz_Zh, s->dz_isq, s->dz_smp, s->dz_rec};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    {
-        PcState& pc = s->pc;
-        void* pcp[] = {pc.L, pc.d, pc.row, pc.e, pc.mark, pc.piv, pc.pivval, pc.pv, pc.pi, pc.inv, pc.isq,
-                       pc.sq, pc.Mt, pc.Mst, pc.part, pc.cT};
-        for (void* p : pcp)
-            if (p) (void)hipFree(p);
-        for (double* p : pc.tops)
-            if (p) (void)hipFree(p);
-        for (double* p : pc.B)
-            if (p) (void)hipFree(p);
-    }
     delete s;
     return RL_OK;
 }
@@ -312,24 +275,22 @@ extern "C" int rl_ski_set_noise(rl_ski* s, const double* noise, const int* lens)
 
 int ski_reserve(rl_ski* s, int nvec) {
     if (nvec <= s->cap && s->G1) return RL_OK;
-    if (s->G1) RL_HIP(hipFree(s->G1));
-    if (s->G2) RL_HIP(hipFree(s->G2));
-    s->G1 = s->G2 = nullptr;
+    s->G1.reset();
+    s->G2.reset();
     s->cap = 0;
-    RL_HIP(hipMalloc((void**)&s->G1, (size_t)nvec * s->max_ngrid * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&s->G2, (size_t)nvec * s->max_ngrid * sizeof(double)));
+    RL_TRY(s->G1.reserve((size_t)nvec * s->max_ngrid));
+    RL_TRY(s->G2.reserve((size_t)nvec * s->max_ngrid));
     s->cap = nvec;
     return RL_OK;
 }
 
 int ski_reserve_perm(rl_ski* s, int nvec) {
     if (!s->permuted || nvec <= s->pcap) return RL_OK;
-    if (s->P1) RL_HIP(hipFree(s->P1));
-    if (s->P2) RL_HIP(hipFree(s->P2));
-    s->P1 = s->P2 = nullptr;
+    s->P1.reset();
+    s->P2.reset();
     s->pcap = 0;
-    RL_HIP(hipMalloc((void**)&s->P1, (size_t)nvec * s->n * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&s->P2, (size_t)nvec * s->n * sizeof(double)));
+    RL_TRY(s->P1.reserve((size_t)nvec * s->n));
+    RL_TRY(s->P2.reserve((size_t)nvec * s->n));
     s->pcap = nvec;
     return RL_OK;
 }
@@ -353,9 +314,9 @@ int ski_wt_int(rl_ski* s, const double* Xp, double* G, int nvec, hipStream_t st,
     // large batch, structured W^T whose workgroup ranges fit LDS: staged form
     // (measured at C5, 129 vectors: see DESIGN.md)
     constexpr int VB = 8;
-    const size_t lds = ((size_t)VB * s->wt_xmax + s->wt_emax) * sizeof(double);
-    if (s->WT_lo != nullptr && s->wt_xmax > 0 && lds <= 64 * 1024 &&
-        s->wt_xmax <= 4 * RL_THREADS &&
+    const size_t lds = ((size_t)VB * s->terms[0].wt_xmax + s->terms[0].wt_emax) * sizeof(double);
+    if (s->terms[0].WT_lo != nullptr && s->terms[0].wt_xmax > 0 && lds <= 64 * 1024 &&
+        s->terms[0].wt_xmax <= 4 * RL_THREADS &&
         ((size_t)s->ngrid * nvec >= ((size_t)1 << 22) || s->kn.staged_wt) && !s->kn.no_staged_wt) {
         trace_once("W^T product: k_spmv_wt_staged");
         static unsigned long long seen = 0;
@@ -372,33 +333,33 @@ int ski_wt_int(rl_ski* s, const double* Xp, double* G, int nvec, hipStream_t st,
         const dim3 grid(gx, ((nvec + VB - 1) / VB + vg - 1) / vg);
 #define RL_WT_STAGED(XPT)                                                                       \
     RL_LAUNCH((k_spmv_wt_staged<VB, XPT>), grid, dim3(RL_THREADS), lds, st,                     \
-              (const int*)s->WT_indptr, (const int*)s->WT_lo, (const double*)s->WT_data,        \
-              s->ngrid, s->n, nvec, Xp, G, s->wt_xmax, vg, bump)
-        if (s->wt_xmax <= RL_THREADS) RL_WT_STAGED(1);
-        else if (s->wt_xmax <= 2 * RL_THREADS) RL_WT_STAGED(2);
+              (const int*)s->terms[0].WT_indptr, (const int*)s->terms[0].WT_lo,                 \
+              (const double*)s->terms[0].WT_data, s->ngrid, s->n, nvec, Xp, G, s->terms[0].wt_xmax, vg, bump)
+        if (s->terms[0].wt_xmax <= RL_THREADS) RL_WT_STAGED(1);
+        else if (s->terms[0].wt_xmax <= 2 * RL_THREADS) RL_WT_STAGED(2);
         else RL_WT_STAGED(4);
 #undef RL_WT_STAGED
         RL_HIP(hipGetLastError());
         return RL_OK;
     }
-    launch_spmv(s->WT_indptr, s->WT_indices, s->WT_data, s->ngrid, s->n, nvec, Xp, G, nullptr,
-                nullptr, st, 0, bump, s->ngrid > 0 ? s->nnzWT / s->ngrid : 0);
+    launch_spmv(s->terms[0].WT_indptr, s->terms[0].WT_indices, s->terms[0].WT_data, s->ngrid, s->n,
+                nvec, Xp, G, nullptr, nullptr, st, 0, bump, s->ngrid > 0 ? s->terms[0].nnzWT / s->ngrid : 0);
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
 // does the W product of a batch take the staged form?
 static bool w_staged_ok(const rl_ski* s, int nvec) {
     constexpr int VB = 8;
-    const size_t lds = (size_t)VB * s->w_xmax * sizeof(double);
-    return s->W4_base != nullptr && s->w_xmax > 0 && lds <= 64 * 1024 &&
-           s->w_xmax <= 4 * RL_THREADS &&
+    const size_t lds = (size_t)VB * s->terms[0].w_xmax * sizeof(double);
+    return s->terms[0].W4_base != nullptr && s->terms[0].w_xmax > 0 && lds <= 64 * 1024 &&
+           s->terms[0].w_xmax <= 4 * RL_THREADS &&
            ((size_t)s->n * nvec >= ((size_t)1 << 22) || s->kn.staged_wt) && !s->kn.no_staged_wt;
 }
 // ... and with MINRES's P inside (k_spmv_w_staged_p: the partial sums' words next to the tile,
 // row accesses by 32-bit byte offsets)?
 static size_t w_staged_p_lds(const rl_ski* s) {
     constexpr int VB = 8;
-    size_t lds = ((size_t)VB * s->w_xmax + (size_t)staged_vgroups() * VB * 8) * sizeof(double);
+    size_t lds = ((size_t)VB * s->terms[0].w_xmax + (size_t)staged_vgroups() * VB * 8) * sizeof(double);
 #if defined(RL_EMU)
     lds += 256 * sizeof(double);
 #endif
@@ -411,7 +372,7 @@ static int ski_w_int(rl_ski* s, const double* G, double* Yp, int nvec, const dou
                      const double* X2p, hipStream_t st) {
     // large batch, structured W: staged form (see ski_wt_int)
     constexpr int VB = 8;
-    const size_t lds = (size_t)VB * s->w_xmax * sizeof(double);
+    const size_t lds = (size_t)VB * s->terms[0].w_xmax * sizeof(double);
     const RpPFuse pf = s->rp_pfuse;          // (by value: the solver clears the handle's copy)
     if (pf.pc != nullptr) {
         // MINRES's P inside the product (the solver checked w_staged_ok): no output vector
@@ -433,10 +394,10 @@ static int ski_w_int(rl_ski* s, const double* G, double* Yp, int nvec, const dou
         const size_t ldsp = w_staged_p_lds(s);
 #define RL_W_STAGED_P(XPT)                                                                      \
     RL_LAUNCH((k_spmv_w_staged_p<VB, XPT>), grid, dim3(RL_THREADS), ldsp, st,                   \
-              (const int*)s->W4_base, (const double*)s->W4_w, s->n, s->ngrid, nvec, G, diag,    \
-              X2p, s->w_xmax, vg, pf)
-        if (s->w_xmax <= RL_THREADS) RL_W_STAGED_P(1);
-        else if (s->w_xmax <= 2 * RL_THREADS) RL_W_STAGED_P(2);
+              (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, s->n, s->ngrid, \
+              nvec, G, diag, X2p, s->terms[0].w_xmax, vg, pf)
+        if (s->terms[0].w_xmax <= RL_THREADS) RL_W_STAGED_P(1);
+        else if (s->terms[0].w_xmax <= 2 * RL_THREADS) RL_W_STAGED_P(2);
         else RL_W_STAGED_P(4);
 #undef RL_W_STAGED_P
         RL_HIP(hipGetLastError());
@@ -458,17 +419,17 @@ static int ski_w_int(rl_ski* s, const double* G, double* Yp, int nvec, const dou
         const dim3 grid(gx, ((nvec + VB - 1) / VB + vg - 1) / vg);
 #define RL_W_STAGED(XPT)                                                                        \
     RL_LAUNCH((k_spmv_w_staged<VB, XPT>), grid, dim3(RL_THREADS), lds, st,                      \
-              (const int*)s->W4_base, (const double*)s->W4_w, s->n, s->ngrid, nvec, G, Yp, diag, \
-              X2p, s->w_xmax, vg)
-        if (s->w_xmax <= RL_THREADS) RL_W_STAGED(1);
-        else if (s->w_xmax <= 2 * RL_THREADS) RL_W_STAGED(2);
+              (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, s->n, s->ngrid, \
+              nvec, G, Yp, diag, X2p, s->terms[0].w_xmax, vg)
+        if (s->terms[0].w_xmax <= RL_THREADS) RL_W_STAGED(1);
+        else if (s->terms[0].w_xmax <= 2 * RL_THREADS) RL_W_STAGED(2);
         else RL_W_STAGED(4);
 #undef RL_W_STAGED
         RL_HIP(hipGetLastError());
         return RL_OK;
     }
-    launch_spmv(s->W_indptr, s->W_indices, s->W_data, s->n, s->ngrid, nvec, G, Yp, diag, X2p,
-                st);
+    launch_spmv(s->terms[0].W_indptr, s->terms[0].W_indices, s->terms[0].W_data, s->n, s->ngrid, nvec,
+                G, Yp, diag, X2p, st);
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
@@ -479,8 +440,8 @@ static int ski_w_int(rl_ski* s, const double* G, double* Yp, int nvec, const dou
 static bool ski_w_poly_ok(const rl_ski* s, int nvec) {
     constexpr int VB = 8;
     const rl_gridop* g = s->g;
-    const size_t lds = ((size_t)VB * s->w_xmax + (size_t)VB * 2 * RL_LR_RMAX) * sizeof(double);
-    return s->W4_base != nullptr && s->w_xmax > 0 && s->w_xmax <= 2 * RL_THREADS &&
+    const size_t lds = ((size_t)VB * s->terms[0].w_xmax + (size_t)VB * 2 * RL_LR_RMAX) * sizeof(double);
+    return s->terms[0].W4_base != nullptr && s->terms[0].w_xmax > 0 && s->terms[0].w_xmax <= 2 * RL_THREADS &&
            lds <= 64 * 1024 && ((size_t)s->n * nvec >= ((size_t)1 << 22) || s->kn.staged_wt) &&
            !s->kn.no_staged_wt &&
            (g->lr_try || g->lr_ok) && g->m >= 4 * RL_THREADS && s->ngrid == g->D * g->m &&
@@ -491,24 +452,25 @@ static int ski_w_poly(rl_ski* s, double* Yp, int nvec, const double* diag, const
     constexpr int VB = 8;
     rl_gridop* g = s->g;
     const int R = g->lr_r;
-    const size_t lds = ((size_t)VB * s->w_xmax + (size_t)VB * 2 * R) * sizeof(double);
+    const size_t lds = ((size_t)VB * s->terms[0].w_xmax + (size_t)VB * 2 * R) * sizeof(double);
     trace_once("W product: k_spmv_w_poly (grid values from the mixed coefficients)");
     const unsigned gx = (s->n + RL_THREADS - 1) / RL_THREADS;
     const int vg = staged_vgroups();
     const dim3 grid(gx, ((nvec + VB - 1) / VB + vg - 1) / vg);
 #define RL_W_POLY(XPT, R_)                                                                      \
     RL_LAUNCH((k_spmv_w_poly<VB, XPT, R_>), grid, dim3(RL_THREADS), lds, st,                    \
-              (const int*)s->W4_base, (const double*)s->W4_w, s->n, s->ngrid, nvec,             \
+              (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, s->n, s->ngrid, \
+              nvec,                                                                             \
               (const double*)g->lr_zhat, (const double*)g->lr_beta, g->D, g->m, Yp, diag, X2p,  \
-              s->w_xmax, vg)
+              s->terms[0].w_xmax, vg)
     if (R == 24) {
-        if (s->w_xmax <= RL_THREADS) RL_W_POLY(1, 24);
+        if (s->terms[0].w_xmax <= RL_THREADS) RL_W_POLY(1, 24);
         else RL_W_POLY(2, 24);
     } else if (R == 32) {
-        if (s->w_xmax <= RL_THREADS) RL_W_POLY(1, 32);
+        if (s->terms[0].w_xmax <= RL_THREADS) RL_W_POLY(1, 32);
         else RL_W_POLY(2, 32);
     } else if (R == 36) {
-        if (s->w_xmax <= RL_THREADS) RL_W_POLY(1, 36);
+        if (s->terms[0].w_xmax <= RL_THREADS) RL_W_POLY(1, 36);
         else RL_W_POLY(2, 36);
     } else {
         return fail(RL_EINVAL, "k_spmv_w_poly: no instantiation for this rank");
@@ -524,7 +486,8 @@ static int ski_w_poly(rl_ski* s, double* Yp, int nvec, const double* diag, const
 // structured W on a 1-D grid, every top row in the polynomial form, a large system)
 bool rp_ok(const rl_ski* s, int nvec) {
     const rl_gridop* g = s->g;
-    return s->extra.empty() && s->W4_base != nullptr && !s->h_base.empty() && !g->wide && !g->lead &&
+    return single_term(s) && s->terms[0].W4_base != nullptr && !s->terms[0].h_base.empty() &&
+           !g->wide && !g->lead &&
            g->lr_try && !g->lr_dirty && g->lr_ok && s->ngrid == g->D * g->m &&
            s->n < (1 << 28) &&          // (k_rp_expand's row accesses carry 32-bit byte offsets)
            // (the batch gate of the structured forms also gates this one: rl_gridop_set_form_gate
@@ -548,12 +511,10 @@ int rp_prepare(rl_ski* s, int nvec) {
         s->rp_R = R;                 // (no table: both kernels compute F from the entries)
     }
     if (s->rp_R != R) {
-        if (s->rp_F) RL_HIP(hipFree(s->rp_F));
-        s->rp_F = nullptr;
         s->rp_R = 0;
-        RL_HIP(hipMalloc((void**)&s->rp_F, (size_t)R * n * sizeof(double)));
+        RL_TRY(s->rp_F.renew((size_t)R * n));
         RL_LAUNCH(k_rp_build, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t) nullptr,
-                  (const int*)s->W4_base, (const double*)s->W4_w, n, m, R,
+                  (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, n, m, R,
                   (const double*)g->lr_beta, s->rp_F);
         RL_HIP(hipGetLastError());
         RL_HIP(hipDeviceSynchronize());
@@ -570,7 +531,7 @@ int rp_prepare(rl_ski* s, int nvec) {
         int i = 0;
         for (int d = 0; d < D; ++d) {
             const int start = i;
-            while (i < n && s->h_base[i] < (d + 1) * m) ++i;
+            while (i < n && s->terms[0].h_base[i] < (d + 1) * m) ++i;
             out_end[d] = i;
             run_ptr[d] = (int)runs.size() / 3;
             for (int r0 = start; r0 < i; r0 += len) {
@@ -582,28 +543,22 @@ int rp_prepare(rl_ski* s, int nvec) {
         run_ptr[D] = (int)runs.size() / 3;
         if (i != n) return fail(RL_EINVAL, "row-polynomial form: rows are not sorted by output");
         if (runs.empty()) return fail(RL_EINVAL, "row-polynomial form: no rows");
-        RL_TRY(upload_raw((void**)&s->rp_runs, runs.data(), runs.size() * sizeof(int)));
-        RL_TRY(upload_raw((void**)&s->rp_run_ptr, run_ptr.data(), run_ptr.size() * sizeof(int)));
-        RL_TRY(upload_raw((void**)&s->rp_out_end, out_end.data(), out_end.size() * sizeof(int)));
+        RL_TRY(s->rp_runs.upload(runs.data(), runs.size()));
+        RL_TRY(s->rp_run_ptr.upload(run_ptr.data(), run_ptr.size()));
+        RL_TRY(s->rp_out_end.upload(out_end.data(), out_end.size()));
         s->rp_nruns = run_ptr[D];
         s->h_run_ptr = run_ptr;
         s->h_out_end = out_end;
     }
     const size_t need = (size_t)s->rp_nruns * nvec * R;
-    if (s->rp_part_cap < need) {
-        if (s->rp_part) RL_HIP(hipFree(s->rp_part));
-        s->rp_part = nullptr;
-        s->rp_part_cap = 0;
-        RL_HIP(hipMalloc((void**)&s->rp_part, need * sizeof(double)));
-        s->rp_part_cap = need;
-    }
+    RL_TRY(s->rp_part.reserve(need));
     RL_TRY(lr_reserve(g, nvec));             // (the mixed coefficients live on the grid handle)
     return RL_OK;
 }
 bool rp_ready(const rl_ski* s, int nvec) {
     return (s->rp_F != nullptr || (s->kn.rp_fly & 2)) && s->rp_R == s->g->lr_r && s->rp_runs != nullptr &&
-           s->rp_part_cap >= (size_t)s->rp_nruns * nvec * s->rp_R &&
-           s->g->lr_zhat_cap >= (size_t)nvec * s->g->D * RL_LR_RMAX;
+           s->rp_part.cap >= (size_t)s->rp_nruns * nvec * s->rp_R &&
+           s->g->lr_zhat.cap >= (size_t)nvec * s->g->D * RL_LR_RMAX;
 }
 template <int R, bool FLYP, bool FLYE>
 static void rp_launch(rl_ski* s, const double* F, const int* base, const double* w4,
@@ -683,11 +638,11 @@ projected:
 static bool caller_order_same(rl_ski* s) {
     if (s->caller_ranges_same < 0) {
         const int n = s->n, m = s->g->m;
-        bool same = (int)s->h_base.size() == n && (int)s->h_perm.size() == n;
+        bool same = (int)s->terms[0].h_base.size() == n && (int)s->h_perm.size() == n;
         for (int a = 0; a < n && same;) {
-            const int d = s->h_base[a] / m;
+            const int d = s->terms[0].h_base[a] / m;
             int b = a;
-            while (b < n && s->h_base[b] / m == d) ++b;
+            while (b < n && s->terms[0].h_base[b] / m == d) ++b;
             for (int i = a; i < b && same; ++i) same = s->h_perm[i] >= a && s->h_perm[i] < b;
             a = b;
         }
@@ -701,8 +656,8 @@ static int ski_rp_mvm(rl_ski* s, bool caller_order, const double* Xp, double* Yp
     trace_once("K~ product: row-polynomial form (k_rp_project / k_lr_mix / k_rp_expand)");
     const bool flyp = (s->kn.rp_fly & 2) != 0, flye = (s->kn.rp_fly & 1) != 0;
     const double* F = caller_order ? s->rp_Fc : s->rp_F;
-    const int* base = caller_order ? s->rp_base_c : s->W4_base;
-    const double* w4 = caller_order ? s->rp_w4_c : s->W4_w;
+    const int* base = caller_order ? s->rp_base_c : s->terms[0].W4_base;
+    const double* w4 = caller_order ? s->rp_w4_c : s->terms[0].W4_w;
 #define RL_RP_CASE(R_)                                                                         \
     case R_:                                                                                    \
         if (flyp) rp_launch<R_, true, true>(s, F, base, w4, Xp, Yp, nvec, diag, st, bump);     \
@@ -722,10 +677,10 @@ static int ski_rp_mvm(rl_ski* s, bool caller_order, const double* Xp, double* Yp
 int ski_mvm_int(rl_ski* s, const double* Xp, double* Yp, int nvec, hipStream_t st, int* bump,
                 bool noise) {
     RL_TRY(ski_reserve(s, nvec));
-    const double* diag = s->has_noise && noise ? s->noise_diag : nullptr;
+    const double* diag = s->has_noise && noise ? s->noise_diag.get() : nullptr;
     // (a pending form decision is taken here, so that the path does not depend on whether an
     // earlier product happened to trigger it)
-    if (s->extra.empty() && !s->g->wide && !s->g->lead && !stream_capturing(st)) RL_TRY(lr_prepare(s->g, nvec));
+    if (single_term(s) && !s->g->wide && !s->g->lead && !stream_capturing(st)) RL_TRY(lr_prepare(s->g, nvec));
     // every top row in the polynomial form, a large system: F M F^T, no interpolation
     // products, no grid vector (rl_rowpoly.h).  (Buffers: the solver prepares them before it
     // captures; a plain product outside a capture prepares them here.)
@@ -741,7 +696,7 @@ int ski_mvm_int(rl_ski* s, const double* Xp, double* Yp, int nvec, hipStream_t s
     // (the solver asked for P inside the W product: the staged kernel, a single term, and the
     // grid vector written -- not the W kernel that expands the polynomial form itself)
     const bool wp = s->rp_pfuse.pc != nullptr;
-    if (wp && (!s->extra.empty() || !w_staged_p_ok(s, nvec)))
+    if (wp && (!single_term(s) || !w_staged_p_ok(s, nvec)))
         return fail(RL_EINVAL, "internal: MINRES update fused into a W product that does not run staged");
     RL_TRY(ski_wt_int(s, Xp, s->G1, nvec, st, bump));
     // a polynomial-form operator hands its mixed coefficients to the W kernel instead of
@@ -758,7 +713,8 @@ int ski_mvm_int(rl_ski* s, const double* Xp, double* Yp, int nvec, hipStream_t s
         if (wp && s->rp_mid) s->rp_mid(st);       // (P's scalar head: k_minres2_ph)
         RL_TRY(ski_w_int(s, s->G2, Yp, nvec, diag, Xp, st));
     }
-    for (const SkiTerm& t : s->extra) {       // Yp += W_t K_t W_t^T Xp
+    for (size_t k = 1; k < s->terms.size(); ++k) {       // Yp += W_t K_t W_t^T Xp
+        const SkiTerm& t = s->terms[k];
         launch_spmv(t.WT_indptr, t.WT_indices, t.WT_data, t.ngrid, s->n, nvec, Xp, s->G1,
                     nullptr, nullptr, st);
         RL_TRY(rl_gridop_mvm(t.g, s->G1, s->G2, nvec, st));
@@ -770,18 +726,10 @@ int ski_mvm_int(rl_ski* s, const double* Xp, double* Yp, int nvec, hipStream_t s
 }
 
 // CSR pair of term `term` (0 = the handle's first term)
-static int term_view(rl_ski* s, int term, SkiTerm* out) {
-    if (term < 0 || term > (int)s->extra.size())
+static int term_view(rl_ski* s, int term, const SkiTerm** out) {
+    if (term < 0 || term >= (int)s->terms.size())
         return fail(RL_EINVAL, "SKI term index out of range");
-    if (term == 0) {
-        out->g = s->g;
-        out->ngrid = s->ngrid;
-        out->W_indptr = s->W_indptr; out->W_indices = s->W_indices; out->W_data = s->W_data;
-        out->WT_indptr = s->WT_indptr; out->WT_indices = s->WT_indices;
-        out->WT_data = s->WT_data;
-    } else {
-        *out = s->extra[term - 1];
-    }
+    *out = &s->terms[term];
     return RL_OK;
 }
 
@@ -789,8 +737,9 @@ extern "C" int rl_ski_apply_wt_term(rl_ski* s, int term, const double* X, double
                                     void* stream) {
     if (!s || !X || !G) return fail(RL_EINVAL, "rl_ski_apply_wt: NULL argument");
     if (nvec <= 0) return nvec == 0 ? RL_OK : fail(RL_EINVAL, "nvec < 0");
-    SkiTerm t;
-    RL_TRY(term_view(s, term, &t));
+    const SkiTerm* tp = nullptr;
+    RL_TRY(term_view(s, term, &tp));
+    const SkiTerm& t = *tp;
     RL_HIP(hipSetDevice(s->g->device));
     hipStream_t st = (hipStream_t)stream;
     if (s->permuted) {
@@ -808,8 +757,9 @@ extern "C" int rl_ski_apply_w_term(rl_ski* s, int term, const double* G, double*
                                    void* stream) {
     if (!s || !G || !Y) return fail(RL_EINVAL, "rl_ski_apply_w: NULL argument");
     if (nvec <= 0) return nvec == 0 ? RL_OK : fail(RL_EINVAL, "nvec < 0");
-    SkiTerm t;
-    RL_TRY(term_view(s, term, &t));
+    const SkiTerm* tp = nullptr;
+    RL_TRY(term_view(s, term, &tp));
+    const SkiTerm& t = *tp;
     RL_HIP(hipSetDevice(s->g->device));
     hipStream_t st = (hipStream_t)stream;
     double* dst = Y;
@@ -843,41 +793,33 @@ extern "C" int rl_ski_mvm(rl_ski* s, const double* X, double* Y, int nvec, void*
     // row permutation of the batch (they were half of this product's time at C5).  The rows of
     // an output are contiguous in both orders, so runs, output borders and the noise array
     // (constant per output) serve both.
-    if (s->extra.empty() && !s->g->wide && !s->g->lead && !stream_capturing(st) && caller_order_same(s)) {
+    if (single_term(s) && !s->g->wide && !s->g->lead && !stream_capturing(st) && caller_order_same(s)) {
         RL_TRY(lr_prepare(s->g, nvec));
         if (rp_ok(s, nvec)) {
             RL_TRY(rp_prepare(s, nvec));
             if (s->kn.rp_fly && (!s->rp_base_c || !s->rp_w4_c)) {
-                // (guarded one by one: a failed second allocation must not leave the first
-                // behind as a sign that both exist)
-                if (!s->rp_base_c)
-                    RL_HIP(hipMalloc((void**)&s->rp_base_c, (size_t)s->n * sizeof(int)));
-                if (!s->rp_w4_c) {
-                    const hipError_t e = hipMalloc((void**)&s->rp_w4_c, (size_t)4 * s->n * sizeof(double));
-                    if (e != hipSuccess) {
-                        s->rp_w4_c = nullptr;
-                        (void)hipFree(s->rp_base_c);
-                        s->rp_base_c = nullptr;
-                        RL_HIP(e);
-                    }
+                // (a failed second allocation must not leave the first behind as a sign that
+                // both exist)
+                RL_TRY(s->rp_base_c.reserve((size_t)s->n));
+                if (s->rp_w4_c.reserve((size_t)4 * s->n) != RL_OK) {
+                    s->rp_base_c.reset();
+                    return RL_EHIP;
                 }
                 RL_LAUNCH(k_rp_permute_entries, dim3((s->n + 255) / 256), dim3(256), 0,
-                          (hipStream_t) nullptr, (const int*)s->W4_base, (const double*)s->W4_w,
+                          (hipStream_t) nullptr, (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w,
                           (const int*)s->perm, s->n, s->rp_base_c, s->rp_w4_c);
                 RL_HIP(hipGetLastError());
                 RL_HIP(hipDeviceSynchronize());
             }
             if (!(s->kn.rp_fly & 2) && s->rp_Fc_R != s->rp_R) {
-                if (s->rp_Fc) RL_HIP(hipFree(s->rp_Fc));
-                s->rp_Fc = nullptr;
                 s->rp_Fc_R = 0;
-                RL_HIP(hipMalloc((void**)&s->rp_Fc, (size_t)s->rp_R * s->n * sizeof(double)));
+                RL_TRY(s->rp_Fc.renew((size_t)s->rp_R * s->n));
                 permute_rows(s, s->rp_F, s->rp_Fc, s->rp_R, 1, (hipStream_t) nullptr);
                 RL_HIP(hipGetLastError());
                 RL_HIP(hipDeviceSynchronize());
                 s->rp_Fc_R = s->rp_R;
             }
-            return ski_rp_mvm(s, true, X, Y, nvec, s->has_noise ? s->noise_diag : nullptr, st,
+            return ski_rp_mvm(s, true, X, Y, nvec, s->has_noise ? s->noise_diag.get() : nullptr, st,
                               nullptr);
         }
     }

@@ -8,73 +8,55 @@
 #include "rl_pivchol.h"
 #include <chrono>
 
-void free_work(SolverWork& w) {
-    for (double*& p : w.vec) { if (p) (void)hipFree(p); p = nullptr; }
-    for (double*& p : w.S) { if (p) (void)hipFree(p); p = nullptr; }
-    for (double*& p : w.part) { if (p) (void)hipFree(p); p = nullptr; }
-    if (w.I) (void)hipFree(w.I);
-    if (w.count) (void)hipFree(w.count);
-    if (w.resid) (void)hipFree(w.resid);
-    w.I = nullptr; w.count = nullptr; w.resid = nullptr; w.lanczos = nullptr;
-}
-
 static size_t ws_cache_limit(const rl_ski* s) {
     const size_t mb = s->kn.ws_cache_mb >= 0 ? (size_t)s->kn.ws_cache_mb : 16384;
     return mb << 20;
 }
 
-// hands the buffers back to the handle (or frees them) and destroys a captured
-// graph at scope exit; kept apart so the plain struct can be copied into launch
-// closures
+// owns the buffers of one solve: hands them back to the handle (or frees them) and
+// destroys a captured graph at scope exit; the launch closures get the plain view
 struct SolverWorkGuard {
     rl_ski* s;
-    SolverWork* w;
+    SolverBufs own;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
-    SolverWorkGuard(rl_ski* s_, SolverWork* w_) : s(s_), w(w_) {}
+    explicit SolverWorkGuard(rl_ski* s_) : s(s_) {}
     ~SolverWorkGuard() {
         if (exec) (void)hipGraphExecDestroy(exec);
         if (graph) (void)hipGraphDestroy(graph);
-        w->lanczos = nullptr;       // owned by the handle (rl_ski::lanczos_buf)
         size_t nv = 0;
-        for (double* p : w->vec) nv += p != nullptr;
+        for (const DevBuf<double>& p : own.vec) nv += p != nullptr;
         const size_t bytes = nv * s->ws_vec_cap * sizeof(double);
-        if (w->I != nullptr && !s->ws_valid && bytes <= ws_cache_limit(s)) {
-            s->ws = *w;
+        if (own.I != nullptr && !s->ws_valid && bytes <= ws_cache_limit(s)) {
+            s->ws = std::move(own);
             s->ws_valid = true;
-        } else {
-            free_work(*w);
-        }
+        }                           // (else `own` frees them)
     }
 };
 
 // `need`: bit i set = vec[i] is used by this call
-static int solver_alloc(rl_ski* s, SolverWork& w, unsigned need, int nrhs, int n, int nblk,
-                        hipStream_t st) {
+static int solver_alloc(rl_ski* s, SolverBufs& own, SolverWork& w, unsigned need, int nrhs, int n,
+                        int nblk, hipStream_t st) {
     const size_t ve = (size_t)nrhs * n, pe = (size_t)nrhs * nblk;
     if (s->ws_valid) {
         if (s->ws_vec_cap >= ve && s->ws_rhs_cap >= (size_t)nrhs && s->ws_part_cap >= pe)
-            w = s->ws;              // checked out; the guard hands it back
-        else
-            free_work(s->ws);
-        s->ws = SolverWork();
+            own = std::move(s->ws); // checked out; the guard hands it back
+        s->ws = SolverBufs();       // (too small: freed)
         s->ws_valid = false;
     }
-    if (w.I == nullptr) {
+    if (own.I == nullptr) {
         s->ws_vec_cap = ve;
         s->ws_rhs_cap = (size_t)nrhs;
         s->ws_part_cap = pe;
-        for (int i = 0; i < 2; ++i)
-            RL_HIP(hipMalloc((void**)&w.S[i], (size_t)nrhs * S_NFIELDS * sizeof(double)));
-        RL_HIP(hipMalloc((void**)&w.I, (size_t)nrhs * I_NFIELDS * sizeof(int)));
-        for (int i = 0; i < 4; ++i)
-            RL_HIP(hipMalloc((void**)&w.part[i], pe * sizeof(double)));
-        RL_HIP(hipMalloc((void**)&w.count, 4 * sizeof(int)));
-        RL_HIP(hipMalloc((void**)&w.resid, (size_t)nrhs * sizeof(double)));
+        for (int i = 0; i < 2; ++i) RL_TRY(own.S[i].reserve((size_t)nrhs * S_NFIELDS));
+        RL_TRY(own.I.reserve((size_t)nrhs * I_NFIELDS));
+        for (int i = 0; i < 4; ++i) RL_TRY(own.part[i].reserve(pe));
+        RL_TRY(own.count.reserve(4));
+        RL_TRY(own.resid.reserve((size_t)nrhs));
     }
     for (int i = 0; i < 10; ++i)
-        if (((need >> i) & 1u) && w.vec[i] == nullptr)
-            RL_HIP(hipMalloc((void**)&w.vec[i], s->ws_vec_cap * sizeof(double)));
+        if (((need >> i) & 1u) && own.vec[i] == nullptr) RL_TRY(own.vec[i].reserve(s->ws_vec_cap));
+    w = own.view();
     RL_HIP(hipMemsetAsync(w.count, 0, 4 * sizeof(int), st));
     RL_HIP(hipMemsetAsync(w.resid, 0, (size_t)nrhs * sizeof(double), st));
     return RL_OK;
@@ -132,7 +114,7 @@ static bool g_is_v2(const rl_gridop* g) { return g->v2; }
 static int poly_round_prepare(rl_ski* s, int nrhs, int max_blk, bool* ok) {
     *ok = false;
     rl_gridop* g = s->g;
-    if (!s->extra.empty() || s->W4_base == nullptr || s->h_base.empty() ||
+    if (!single_term(s) || s->terms[0].W4_base == nullptr || s->terms[0].h_base.empty() ||
         !g->lr_round_try || s->poly_nblk < 0 || s->kn.no_poly_round || g->kn.no_poly_round)
         return RL_OK;
     if (s->poly_nblk == 0) {
@@ -142,7 +124,7 @@ static int poly_round_prepare(rl_ski* s, int nrhs, int max_blk, bool* ok) {
         for (int d = 0; d < D; ++d) {
             ob[d] = (int)tab.size() / RL_PT;
             const int start = i;
-            while (i < n && s->h_base[i] < (d + 1) * m) ++i;
+            while (i < n && s->terms[0].h_base[i] < (d + 1) * m) ++i;
             const int cnt = i - start;
             // (1024 rows per block; 512 / 256 measured slower at C2: 8.1 / 11.1 against
             // 7.0 ms per step -- every workgroup repeats the mix of its system)
@@ -154,9 +136,9 @@ static int poly_round_prepare(rl_ski* s, int nrhs, int max_blk, bool* ok) {
                 tab.push_back(r1);
                 tab.push_back(d);
                 // grid points (within the output) the block's rows touch
-                const int gfirst = s->h_base[r0] - d * m;
+                const int gfirst = s->terms[0].h_base[r0] - d * m;
                 tab.push_back(gfirst);
-                tab.push_back(s->h_base[r1 - 1] - d * m + 4 - gfirst);
+                tab.push_back(s->terms[0].h_base[r1 - 1] - d * m + 4 - gfirst);
             }
         }
         ob[D] = (int)tab.size() / RL_PT;
@@ -164,21 +146,15 @@ static int poly_round_prepare(rl_ski* s, int nrhs, int max_blk, bool* ok) {
             s->poly_nblk = -1;
             return RL_OK;
         }
-        RL_TRY(upload_raw((void**)&s->poly_tab, tab.data(), tab.size() * sizeof(int)));
-        RL_TRY(upload_raw((void**)&s->poly_ob, ob.data(), ob.size() * sizeof(int)));
+        RL_TRY(s->poly_tab.upload(tab.data(), tab.size()));
+        RL_TRY(s->poly_ob.upload(ob.data(), ob.size()));
         s->poly_nblk = (int)tab.size() / RL_PT;
     }
     if (s->poly_nblk > std::max(max_blk, RL_SOLVER_THREADS)) return RL_OK;
     RL_TRY(lr_ensure(g));
     if (!g->lr_ok || g->lr_r != RL_LR_RS) return RL_OK;
     const size_t need = (size_t)nrhs * s->poly_nblk * RL_LR_RS;
-    if (s->poly_part_cap < need) {
-        if (s->poly_part) RL_HIP(hipFree(s->poly_part));
-        s->poly_part = nullptr;
-        s->poly_part_cap = 0;
-        RL_HIP(hipMalloc((void**)&s->poly_part, need * sizeof(double)));
-        s->poly_part_cap = need;
-    }
+    RL_TRY(s->poly_part.reserve(need));
     *ok = true;
     return RL_OK;
 }
@@ -206,15 +182,15 @@ static int minres2_round(rl_ski* s, const Minres2Bufs& mb, int nrhs, int n, int 
         // P: three grid kernels, P, B
         rl_gridop* g = s->g;
         Gather gs;
-        gs.indptr = s->WT_indptr;
-        gs.indices = s->WT_indices;
-        gs.vals = s->WT_data;
+        gs.indptr = s->terms[0].WT_indptr;
+        gs.indices = s->terms[0].WT_indices;
+        gs.vals = s->terms[0].WT_data;
         gs.src = yin;
         gs.n = n;
-        gs.nnz = s->nnzWT;
-        gs.lo = s->WT_lo;
+        gs.nnz = s->terms[0].nnzWT;
+        gs.lo = s->terms[0].WT_lo;
         MixParams mp{g->Q, g->nfac, g->spec, g->facA, g->facW, g->facQ, g->kappa,
-                     g->mixtab_ok ? g->mixtab : nullptr,
+                     g->mixtab_ok ? g->mixtab.get() : nullptr,
                      g->mixtab_ok ? g->mixtab + (size_t)g->D * g->L : nullptr};
         if (g->v2)
             RL_TRY(mvm_chunk_v2(g, mp, nullptr, s->G2, nrhs, ((size_t)nrhs + 1) / 2, st, &gs,
@@ -362,17 +338,16 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
     const bool use_graph = !s->kn.no_graph;
 
     SolverWork w;
-    SolverWorkGuard guard(s, &w);
+    SolverWorkGuard guard(s);
     // (vec[5]: v of the four-kernel MINRES only; vec[8], vec[9]: right-hand sides
     // and solutions in the handle's internal row order)
     unsigned need = method == RL_MINRES ? 0x5bu : 0x0fu;      // two-kernel MINRES: 0, 1, 3, 4, 6
     if (method == RL_MINRES && s->kn.minres_v1) need = 0x7fu;
     if (s->permuted) need |= 0x300u;
-    RL_TRY(solver_alloc(s, w, need, nrhs, n, nblk, st));
+    RL_TRY(solver_alloc(s, guard.own, w, need, nrhs, n, nblk, st));
     // everything the operator product allocates lazily must exist before capture
     RL_TRY(ski_reserve(s, nrhs));
-    RL_TRY(gridop_prepare(s->g, nrhs));
-    for (const SkiTerm& t : s->extra) RL_TRY(gridop_prepare(t.g, nrhs));
+    for (const SkiTerm& t : s->terms) RL_TRY(gridop_prepare(t.g, nrhs));
     if (rp_ok(s, nrhs)) RL_TRY(rp_prepare(s, nrhs));       // (row-polynomial rounds: F, runs, partial sums)
     int active = nrhs;
     int done = 0;          // iterations issued so far
@@ -403,27 +378,27 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
         mb.lanczos_cap = 0;
         // the W product rides inside P when the problem is small enough to be
         // launch-bound (a big one amortises the CSR over 8 vectors in k_spmv<8>)
-        const bool fuse_w = s->extra.empty() && (size_t)n * nrhs < ((size_t)1 << 22) &&
+        const bool fuse_w = single_term(s) && (size_t)n * nrhs < ((size_t)1 << 22) &&
                             !s->kn.no_fuse_w;
-        mb.W_indptr = fuse_w ? s->W_indptr : nullptr;
+        mb.W_indptr = fuse_w ? s->terms[0].W_indptr.get() : nullptr;
         // ... and W^T inside the first grid kernel when that is a k2_cols_fwd and
         // the batch is one chunk (the operator input is then the rotating buffer
         // itself: no copy of the new Lanczos vector)
         // (only while the rows of W^T are short -- about as many data points as grid
         // points: a row of 30 entries, as on the weather workload, is a serial chain
         // of gathers inside the transform kernel: 1.45 vs 1.23 s per fit)
-        const bool short_rows = (size_t)s->nnzWT <= (size_t)8 * s->ngrid;
+        const bool short_rows = (size_t)s->terms[0].nnzWT <= (size_t)8 * s->ngrid;
         const bool fuse_wt = fuse_w && short_rows && s->g->Q >= 1 && !s->g->wide && !s->g->lead &&
                              ((size_t)nrhs + 1) / 2 <= s->g->chunk_pairs &&
                              !s->kn.no_fuse_wt;
         mb.fuse_wt = fuse_wt ? 1 : 0;
-        mb.W_indices = s->W_indices;
-        mb.W_data = s->W_data;
+        mb.W_indices = s->terms[0].W_indices;
+        mb.W_data = s->terms[0].W_data;
         mb.W_nnz = s->nnz;
-        mb.W4_base = s->W4_base;
-        mb.W4_w = s->W4_w;
+        mb.W4_base = s->terms[0].W4_base;
+        mb.W4_w = s->terms[0].W4_w;
         mb.g = s->G2;
-        mb.eps = s->has_noise ? s->noise_diag : nullptr;
+        mb.eps = s->has_noise ? s->noise_diag.get() : nullptr;
         mb.ngrid = s->ngrid;
         mb.poly_part = nullptr;
         mb.giter2 = w.count + 3;
@@ -440,7 +415,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
         // single-term operator, W as its own kernel, noise in a few constant runs
         // (one per output): the noise term moves into P
         mb.eps_runs = 0;
-        if (!fuse_w && s->extra.empty() && s->has_noise && !s->eps_end.empty()) {
+        if (!fuse_w && single_term(s) && s->has_noise && !s->eps_end.empty()) {
             mb.eps_runs = (int)s->eps_end.size();
             for (int k = 0; k < mb.eps_runs; ++k) {
                 mb.eps_end[k] = s->eps_end[k];
@@ -449,13 +424,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
         }
         if (lanczos_out != nullptr) {
             const size_t bytes = (size_t)nrhs * lanczos_cap * 2 * sizeof(double);
-            if (s->lanczos_bytes < bytes) {
-                if (s->lanczos_buf) RL_HIP(hipFree(s->lanczos_buf));
-                s->lanczos_buf = nullptr;
-                s->lanczos_bytes = 0;
-                RL_HIP(hipMalloc((void**)&s->lanczos_buf, bytes));
-                s->lanczos_bytes = bytes;
-            }
+            RL_TRY(s->lanczos_buf.reserve(bytes / sizeof(double)));
             w.lanczos = s->lanczos_buf;
             RL_HIP(hipMemsetAsync(w.lanczos, 0, bytes, st));
             mb.lanczos = w.lanczos;
@@ -473,13 +442,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
         if (mb.W_indptr == nullptr && mb.poly_part == nullptr && rp_ok(s, nrhs) && rp_ready(s, nrhs) &&
             !(s->kn.rp_fly & 2) && !s->kn.no_rp_fuse) {
             const size_t need = (size_t)nrhs * (s->rp_nruns + 1);
-            if (s->rp_nrm_cap < need) {
-                if (s->rp_nrm) RL_HIP(hipFree(s->rp_nrm));
-                s->rp_nrm = nullptr;
-                s->rp_nrm_cap = 0;
-                RL_HIP(hipMalloc((void**)&s->rp_nrm, need * sizeof(double)));
-                s->rp_nrm_cap = need;
-            }
+            RL_TRY(s->rp_nrm.reserve(need));
             mb.fuse_b = 1;
             mb.coef = s->rp_nrm;
             mb.nrmB = s->rp_nrm + nrhs;
@@ -495,13 +458,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
                 // ... and P inside the expansion (k_minres2_ph + k_rp_expand<.., true>)
                 const int np = (n + 255) / 256;
                 const size_t needp = (size_t)nrhs * (RL_RP_PCW + 3 * (size_t)np);
-                if (s->rp_pp_cap < needp) {
-                    if (s->rp_pp) RL_HIP(hipFree(s->rp_pp));
-                    s->rp_pp = nullptr;
-                    s->rp_pp_cap = 0;
-                    RL_HIP(hipMalloc((void**)&s->rp_pp, needp * sizeof(double)));
-                    s->rp_pp_cap = needp;
-                }
+                RL_TRY(s->rp_pp.reserve(needp));
                 RL_HIP(hipMemsetAsync(s->rp_pp, 0, needp * sizeof(double), st));
                 mb.fuse_p = nrhs;                 // (the head kernel's grid)
                 mb.pc = s->rp_pp;
@@ -512,7 +469,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
                 trace_once("minres round: P inside the row-polynomial expansion (k_minres2_ph)");
             }
         } else if (mb.W_indptr == nullptr && mb.poly_part == nullptr && s->kn.w_pfuse &&
-                   s->extra.empty() && w_staged_p_ok(s, nrhs) &&
+                   single_term(s) && w_staged_p_ok(s, nrhs) &&
                    // (an operator wholly in the polynomial form has better rounds: row-polynomial
                    // ones, or the W kernel that expands the coefficients itself)
                    !(s->g->lr_ok && !s->g->lr_dirty) && !(rp_ok(s, nrhs) && rp_ready(s, nrhs))) {
@@ -520,13 +477,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
             // the staged W product (k_minres2_ph + k_spmv_w_staged_p), B = k_minres2_bh + k_minres2_bv
             const int np = (n + RL_THREADS - 1) / RL_THREADS;
             const size_t needp = (size_t)nrhs * (RL_RP_PCW + 1 + 3 * (size_t)np);
-            if (s->rp_pp_cap < needp) {
-                if (s->rp_pp) RL_HIP(hipFree(s->rp_pp));
-                s->rp_pp = nullptr;
-                s->rp_pp_cap = 0;
-                RL_HIP(hipMalloc((void**)&s->rp_pp, needp * sizeof(double)));
-                s->rp_pp_cap = needp;
-            }
+            RL_TRY(s->rp_pp.reserve(needp));
             RL_HIP(hipMemsetAsync(s->rp_pp, 0, needp * sizeof(double), st));
             mb.fuse_p = nrhs;
             mb.pc = s->rp_pp;
@@ -636,13 +587,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
         mb.lanczos_cap = 0;
         if (lanczos_out != nullptr) {
             const size_t bytes = (size_t)nrhs * lanczos_cap * 2 * sizeof(double);
-            if (s->lanczos_bytes < bytes) {
-                if (s->lanczos_buf) RL_HIP(hipFree(s->lanczos_buf));
-                s->lanczos_buf = nullptr;
-                s->lanczos_bytes = 0;
-                RL_HIP(hipMalloc((void**)&s->lanczos_buf, bytes));
-                s->lanczos_bytes = bytes;
-            }
+            RL_TRY(s->lanczos_buf.reserve(bytes / sizeof(double)));
             w.lanczos = s->lanczos_buf;
             RL_HIP(hipMemsetAsync(w.lanczos, 0, bytes, st));
             mb.lanczos = w.lanczos;
@@ -846,14 +791,14 @@ static void rp_project_plain(rl_ski* s, const double* Xp, int nvec, hipStream_t 
         const size_t lds1 = (((size_t)16 * NT + RL_RP_VG) * RL_RP_LD + RL_RP_TILE) * sizeof(double);
         RL_LAUNCH((k_rp_project1<R, false>), dim3(s->rp_nruns), dim3(256), lds1, st, Xp, s->n, nvec,
                   F_, (const int*)s->rp_runs, part_, (int*)nullptr,
-                  (const int*)s->W4_base, (const double*)s->W4_w, g->m, beta_, nofz);
+                  (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, g->m, beta_, nofz);
         return;
     }
     const size_t lds = (((size_t)16 * NT + 2 * RL_RP_VG) * RL_RP_LD + RL_RP_TILE) * sizeof(double);
     const int vblk = RL_RP_NG(R) * RL_RP_VG;
     RL_LAUNCH((k_rp_project<R, false>), dim3(8 * ((s->rp_nruns + 7) / 8) * ((nvec + vblk - 1) / vblk)),
               dim3(256), lds, st, Xp, s->n, nvec, F_, (const int*)s->rp_runs,
-              s->rp_nruns, part_, (int*)nullptr, (const int*)s->W4_base, (const double*)s->W4_w,
+              s->rp_nruns, part_, (int*)nullptr, (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w,
               g->m, beta_, nofz);
 }
 // Yp = F zhat + diag (.) X2
@@ -867,19 +812,19 @@ static void rp_expand_plain(rl_ski* s, const double* zhat, double* Yp, int nvec,
     if (Ftab != nullptr) {
         RL_LAUNCH((k_rp_expand<R, false, false, true>), dim3((s->n + 255) / 256), dim3(256), 0, st, zhat,
                   Ftab, s->n, nvec, g->D, (const int*)s->rp_out_end, Yp, diag, X2,
-                  s->kn.rp_stagger, (const int*)s->W4_base, (const double*)s->W4_w, g->m,
+                  s->kn.rp_stagger, (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, g->m,
                   (const double*)g->lr_beta, nopf);
         return;
     }
     if (s->kn.rp_fly & 1)
         RL_LAUNCH((k_rp_expand<R, true, false, true>), dim3((s->n + 255) / 256), dim3(256), 0, st, zhat,
                   (const double*)s->rp_F, s->n, nvec, g->D, (const int*)s->rp_out_end, Yp, diag, X2,
-                  s->kn.rp_stagger, (const int*)s->W4_base, (const double*)s->W4_w, g->m,
+                  s->kn.rp_stagger, (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, g->m,
                   (const double*)g->lr_beta, nopf);
     else
         RL_LAUNCH((k_rp_expand<R, false, false, true>), dim3((s->n + 255) / 256), dim3(256), 0, st, zhat,
                   (const double*)s->rp_F, s->n, nvec, g->D, (const int*)s->rp_out_end, Yp, diag, X2,
-                  s->kn.rp_stagger, (const int*)s->W4_base, (const double*)s->W4_w, g->m,
+                  s->kn.rp_stagger, (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, g->m,
                   (const double*)g->lr_beta, nopf);
 }
 #define RL_DZ_RANKS(CALL)                                                               \
@@ -1118,23 +1063,11 @@ static int hz_rank(const rl_ski* s) {
     }
     return 0;
 }
-template <class T>
-static int hz_grow(T** p, size_t count) {
-    if (*p) RL_HIP(hipFree(*p));
-    *p = nullptr;
-    RL_HIP(hipMalloc((void**)p, count * sizeof(T)));
-    return RL_OK;
-}
-
 // the square-root factor's map of the current factorisation on the device (empty: not asked for)
 static int dz_upload_sample_map(rl_ski* s, const std::vector<double>& Zh) {
     s->dz_Zh_valid = false;
     if (Zh.empty()) return RL_OK;
-    if (s->dz_Zh_cap < Zh.size()) {
-        s->dz_Zh_cap = 0;
-        RL_TRY(hz_grow(&s->dz_Zh, Zh.size()));
-        s->dz_Zh_cap = Zh.size();
-    }
+    RL_TRY(s->dz_Zh.reserve(Zh.size()));
     RL_HIP(hipMemcpy(s->dz_Zh, Zh.data(), Zh.size() * sizeof(double), hipMemcpyHostToDevice));
     s->dz_Zh_valid = true;
     return RL_OK;
@@ -1146,11 +1079,11 @@ static int hz_reserve(rl_ski* s, int nvec) {
     if (s->hz_vec_cap >= cap && s->hz_part != nullptr) return RL_OK;
     s->hz_vec_cap = 0;
     const size_t nb = (size_t)s->hz_R / RL_HZ_BLK;
-    RL_TRY(hz_grow(&s->hz_part, nb * s->rp_nruns * cap * RL_HZ_BLK));
-    RL_TRY(hz_grow(&s->hz_zhat, nb * (cap + 16) * s->g->D * RL_HZ_BLK));
-    RL_TRY(hz_grow(&s->hz_tmp, cap * s->n));      // (the block-by-block expansion's)
-    RL_TRY(hz_grow(&s->hz_S, cap * s->g->D * s->hz_R));
-    RL_TRY(hz_grow(&s->hz_P, (size_t)RL_HZ_FS * cap * s->g->D * s->hz_R));
+    RL_TRY(s->hz_part.renew(nb * s->rp_nruns * cap * RL_HZ_BLK));
+    RL_TRY(s->hz_zhat.renew(nb * (cap + 16) * s->g->D * RL_HZ_BLK));
+    RL_TRY(s->hz_tmp.renew(cap * s->n));      // (the block-by-block expansion's)
+    RL_TRY(s->hz_S.renew(cap * s->g->D * s->hz_R));
+    RL_TRY(s->hz_P.renew((size_t)RL_HZ_FS * cap * s->g->D * s->hz_R));
     s->hz_vec_cap = cap;
     return RL_OK;
 }
@@ -1208,19 +1141,19 @@ static int hz_basis(rl_ski* s) {
         const double need = 2.0 * (double)R * n * sizeof(double) + 2.0 * (double)rows * m * sizeof(double) + 1e9;
         if ((double)free_b < need) { s->hz_why = "not enough free device memory for the larger basis' table"; return RL_OK; }
     }
-    RL_TRY(upload(&s->hz_phi, phi));
-    RL_TRY(upload(&s->hz_beta, beta));
+    RL_TRY(s->hz_phi.upload(phi));
+    RL_TRY(s->hz_beta.upload(beta));
     s->hz_hnu = nu;
-    RL_TRY(hz_grow(&s->hz_tphi, (size_t)rows * m));
-    RL_TRY(hz_grow(&s->hz_C, (size_t)R * R));
-    RL_TRY(hz_grow(&s->hz_F, (size_t)R * n));
+    RL_TRY(s->hz_tphi.reserve((size_t)rows * m));
+    RL_TRY(s->hz_C.reserve((size_t)R * R));
+    RL_TRY(s->hz_F.reserve((size_t)R * n));
     {
         std::vector<double> ones((size_t)n, 1.0);
-        RL_TRY(upload(&s->hz_ones, ones));
+        RL_TRY(s->hz_ones.upload(ones));
     }
     hipStream_t st = nullptr;
-    RL_LAUNCH(k_rp_build, dim3((n + 255) / 256), dim3(256), 0, st, (const int*)s->W4_base,
-              (const double*)s->W4_w, n, m, R, (const double*)s->hz_beta, s->hz_F);
+    RL_LAUNCH(k_rp_build, dim3((n + 255) / 256), dim3(256), 0, st, (const int*)s->terms[0].W4_base,
+              (const double*)s->terms[0].W4_w, n, m, R, (const double*)s->hz_beta, s->hz_F);
     RL_HIP(hipGetLastError());
     RL_TRY(hz_reserve(s, RL_HZ_BLK));
     // U_d[(rb, j)][(cb, v)] = sum over the runs c of output d of part[c][v][j]: half cb of the
@@ -1337,11 +1270,7 @@ static int hz_try(rl_ski* s, const std::vector<double>& eps, const std::vector<i
     RL_TRY(dz_upload_sample_map(s, Zh));
     for (double v : Zs)
         if (!std::isfinite(v)) { *why = "the solve map is not finite"; return RL_OK; }
-    if (s->dz_Zt_cap < Zs.size()) {
-        s->dz_Zt_cap = 0;
-        RL_TRY(hz_grow(&s->dz_Zt, Zs.size()));
-        s->dz_Zt_cap = Zs.size();
-    }
+    RL_TRY(s->dz_Zt.reserve(Zs.size()));
     RL_HIP(hipMemcpy(s->dz_Zt, Zs.data(), Zs.size() * sizeof(double), hipMemcpyHostToDevice));
     s->dz_logdet = logdet;
     s->dz_cond = (pmax / pmin) * (pmax / pmin);
@@ -1407,8 +1336,8 @@ static int hz_apply(rl_ski* s, const double* in, double* out, int nvec, hipStrea
 // ---------------------------------------------------------------------------
 static unsigned long long pc_param_sum(const rl_ski* s) {
     // (versions only grow: the sum moves with every update of any of the handle's grids)
-    unsigned long long v = s->g->pc_ver;
-    for (const SkiTerm& t : s->extra) v += t.g->pc_ver;
+    unsigned long long v = 0;
+    for (const SkiTerm& t : s->terms) v += t.g->pc_ver;
     return v;
 }
 static int pc_chunk_rows(int n) {
@@ -1417,26 +1346,18 @@ static int pc_chunk_rows(int n) {
 }
 // partial sums and coefficients of nvec vectors
 static int pc_reserve(rl_ski* s, int nvec) {
-    PcState& pc = s->pc;
+    PcState* pc = &s->pc;
     const int nvp = (nvec + 15) / 16 * 16;
     const int nchunk = (s->n + pc_chunk_rows(s->n) - 1) / pc_chunk_rows(s->n);
-    const size_t need = (size_t)nchunk * nvp * pc.kp, needc = (size_t)pc.kp * nvp;
-    if (pc.part_cap < need) {
-        pc.part_cap = 0;
-        RL_TRY(hz_grow(&pc.part, need));
-        pc.part_cap = need;
-    }
-    if (pc.cT_cap < needc) {
-        pc.cT_cap = 0;
-        RL_TRY(hz_grow(&pc.cT, needc));
-        pc.cT_cap = needc;
-    }
+    const size_t need = (size_t)nchunk * nvp * pc->kp, needc = (size_t)pc->kp * nvp;
+    RL_TRY(pc->part.reserve(need));
+    RL_TRY(pc->cT.reserve(needc));
     return RL_OK;
 }
 // part[chunk][v][j] = sum_{i in chunk} L[j][i] sc_i X[v][i]  (buffers: pc_reserve)
 static void pc_project(rl_ski* s, const double* X, const double* sc, int nvec, hipStream_t st) {
-    PcState& pc = s->pc;
-    const int n = s->n, nvp = (nvec + 15) / 16 * 16, kp = pc.kp, rows = pc_chunk_rows(n);
+    PcState* pc = &s->pc;
+    const int n = s->n, nvp = (nvec + 15) / 16 * 16, kp = pc->kp, rows = pc_chunk_rows(n);
     const int nchunk = (n + rows - 1) / rows, nvt = nvp / 16;
     const int JT = kp <= 64 ? 1 : kp <= 128 ? 2 : 4;
     // (16 JT NVT accumulation registers a lane: at most 144)
@@ -1444,8 +1365,8 @@ static void pc_project(rl_ski* s, const double* X, const double* sc, int nvec, h
     const dim3 grid((nvt + NVT - 1) / NVT, nchunk);
 #define RL_PC_PROJ(NVT_, JT_)                                                                      \
     if (NVT == NVT_ && JT == JT_)                                                                  \
-        RL_LAUNCH((k_pc_project<NVT_, JT_>), grid, dim3(256), 0, st, X, sc, (const double*)pc.L, n, \
-                  nvec, nvp, kp, rows, pc.part)
+        RL_LAUNCH((k_pc_project<NVT_, JT_>), grid, dim3(256), 0, st, X, sc, (const double*)pc->L, n, \
+                  nvec, nvp, kp, rows, pc->part)
     RL_PC_PROJ(1, 1); RL_PC_PROJ(2, 1); RL_PC_PROJ(4, 1); RL_PC_PROJ(9, 1);
     RL_PC_PROJ(1, 2); RL_PC_PROJ(2, 2); RL_PC_PROJ(4, 2); RL_PC_PROJ(9, 2);
     RL_PC_PROJ(1, 4); RL_PC_PROJ(2, 4); RL_PC_PROJ(4, 4);
@@ -1455,20 +1376,20 @@ static void pc_project(rl_ski* s, const double* X, const double* sc, int nvec, h
 // Mt: the map transposed, dev [kp][kp]; b NULL = 1
 static int pc_apply(rl_ski* s, const double* in, double* out, int nvec, hipStream_t st, const double* Mt,
                     const double* sc, const double* a, const double* b) {
-    PcState& pc = s->pc;
-    const int n = s->n, nvp = (nvec + 15) / 16 * 16, kp = pc.kp, rows = pc_chunk_rows(n);
+    PcState* pc = &s->pc;
+    const int n = s->n, nvp = (nvec + 15) / 16 * 16, kp = pc->kp, rows = pc_chunk_rows(n);
     const int nchunk = (n + rows - 1) / rows, nvt = nvp / 16;
-    if (pc.part_cap < (size_t)nchunk * nvp * kp || pc.cT_cap < (size_t)kp * nvp)
+    if (pc->part.cap < (size_t)nchunk * nvp * kp || pc->cT.cap < (size_t)kp * nvp)
         return fail(RL_EINVAL, "internal: pivoted-Cholesky buffers not reserved");
     pc_project(s, in, sc, nvec, st);
-    RL_LAUNCH(k_pc_map, dim3(nvp), dim3(256), (size_t)kp * sizeof(double), st, (const double*)pc.part,
-              nchunk, nvp, kp, Mt, pc.cT);
+    RL_LAUNCH(k_pc_map, dim3(nvp), dim3(256), (size_t)kp * sizeof(double), st, (const double*)pc->part,
+              nchunk, nvp, kp, Mt, pc->cT);
     const int NVT = nvt >= 9 ? 9 : nvt >= 3 ? 3 : nvt >= 2 ? 2 : 1;
     const dim3 grid((n + 127) / 128, (nvt + NVT - 1) / NVT);
 #define RL_PC_EXP(NVT_)                                                                            \
     if (NVT == NVT_)                                                                               \
-        RL_LAUNCH((k_pc_expand<NVT_>), grid, dim3(256), 0, st, (const double*)pc.cT,               \
-                  (const double*)pc.L, n, nvec, nvp, kp, in, a, b, out)
+        RL_LAUNCH((k_pc_expand<NVT_>), grid, dim3(256), 0, st, (const double*)pc->cT,               \
+                  (const double*)pc->L, n, nvec, nvp, kp, in, a, b, out)
     RL_PC_EXP(1); RL_PC_EXP(2); RL_PC_EXP(3); RL_PC_EXP(9);
 #undef RL_PC_EXP
     RL_HIP(hipGetLastError());
@@ -1477,66 +1398,52 @@ static int pc_apply(rl_ski* s, const double* in, double* out, int nvec, hipStrea
 
 // one W K W^T term as k_pc_diag reads it; uploads what the grid keeps on the host only
 static int pc_term(rl_ski* s, int t, PcTerm* out) {
-    PcState& pc = s->pc;
-    rl_gridop* g = t == 0 ? s->g : s->extra[t - 1].g;
+    PcState* pc = &s->pc;
+    const SkiTerm& term = s->terms[t];
+    rl_gridop* g = term.g;
     const int Q = g->Q, D = g->D, m = g->m;
-    if ((int)pc.tops.size() <= t) {
-        pc.tops.resize(t + 1, nullptr);
-        pc.tops_cap.resize(t + 1, 0);
-        pc.B.resize(t + 1, nullptr);
-        pc.B_cap.resize(t + 1, 0);
+    if ((int)pc->tops.size() <= t) {
+        pc->tops.resize(t + 1);
+        pc->B.resize(t + 1);
     }
     const size_t nt = (size_t)Q * m, nb = (size_t)Q * D * D;
     const double* tops = g->tops;
     if (g->lead || g->wide || tops == nullptr) {
-        if (pc.tops_cap[t] < nt) {
-            pc.tops_cap[t] = 0;
-            RL_TRY(hz_grow(&pc.tops[t], nt));
-            pc.tops_cap[t] = nt;
-        }
-        RL_HIP(hipMemcpy(pc.tops[t], g->h_tops.data(), nt * sizeof(double), hipMemcpyHostToDevice));
-        tops = pc.tops[t];
+        RL_TRY(pc->tops[t].reserve(nt));
+        RL_HIP(hipMemcpy(pc->tops[t], g->h_tops.data(), nt * sizeof(double), hipMemcpyHostToDevice));
+        tops = pc->tops[t];
     }
-    if (pc.B_cap[t] < nb) {
-        pc.B_cap[t] = 0;
-        RL_TRY(hz_grow(&pc.B[t], nb));
-        pc.B_cap[t] = nb;
-    }
-    RL_HIP(hipMemcpy(pc.B[t], g->pc_hB.data(), nb * sizeof(double), hipMemcpyHostToDevice));
+    RL_TRY(pc->B[t].reserve(nb));
+    RL_HIP(hipMemcpy(pc->B[t], g->pc_hB.data(), nb * sizeof(double), hipMemcpyHostToDevice));
     out->tops = tops;
-    out->B = pc.B[t];
+    out->B = pc->B[t];
     out->m = m;
     out->Q = Q;
     // (a 3-D handle's geo holds its inner sizes, m / (m1 m2) leading planes; 1-D: m1 == 0)
     out->e1 = g->geo.m1 > 0 ? g->geo.m1 : 1;
     out->e2 = g->geo.m1 > 0 ? g->geo.m2 : m;
-    if (t == 0) {
-        out->indptr = s->W_indptr; out->indices = s->W_indices; out->w = s->W_data;
-    } else {
-        const SkiTerm& e = s->extra[t - 1];
-        out->indptr = e.W_indptr; out->indices = e.W_indices; out->w = e.W_data;
-    }
+    out->indptr = term.W_indptr; out->indices = term.W_indices; out->w = term.W_data;
     return RL_OK;
 }
 
 // builds (or rebuilds) the preconditioner for the current parameters and noise; *ok = false
 // with a reason when there is none
 static int pc_ensure(rl_ski* s, bool* ok, const char** why) {
-    PcState& pc = s->pc;
+    PcState* pc = &s->pc;
     rl_gridop* g = s->g;
     *ok = false;
     *why = "";
     const int n = s->n;
     const unsigned long long psum = pc_param_sum(s);
-    const int k = std::min(pc.rank, n), kp = (k + 15) / 16 * 16;
-    if (pc.valid && pc.param_sum == psum && pc.noise_ver == s->noise_ver && pc.k == k) {
+    const int k = std::min(pc->rank, n), kp = (k + 15) / 16 * 16;
+    if (pc->valid && pc->param_sum == psum && pc->noise_ver == s->noise_ver && pc->k == k) {
         *ok = true;
         return RL_OK;
     }
-    pc.valid = false;
-    const int nterm = 1 + (int)s->extra.size();
+    pc->valid = false;
+    const int nterm = (int)s->terms.size();
     for (int t = 0; t < nterm; ++t) {
-        const rl_gridop* gt = t == 0 ? g : s->extra[t - 1].g;
+        const rl_gridop* gt = s->terms[t].g;
         if (gt->Q < 1 || gt->h_tops.size() < (size_t)gt->Q * gt->m ||
             gt->pc_hB.size() < (size_t)gt->Q * gt->D * gt->D) {
             *why = "pivoted-Cholesky preconditioner: no parameters set";
@@ -1553,58 +1460,52 @@ static int pc_ensure(rl_ski* s, bool* ok, const char** why) {
     hipStream_t st = nullptr;
     using clk = std::chrono::steady_clock;
     const auto t_start = clk::now();
-    if (pc.eps_ver != s->noise_ver || pc.inv == nullptr) {
+    if (pc->eps_ver != s->noise_ver || pc->inv == nullptr) {
         std::vector<double> v((size_t)n);
-        if (!pc.inv) {
-            RL_TRY(hz_grow(&pc.inv, (size_t)n));
-            RL_TRY(hz_grow(&pc.isq, (size_t)n));
-            RL_TRY(hz_grow(&pc.sq, (size_t)n));
+        if (!pc->inv) {
+            RL_TRY(pc->inv.reserve((size_t)n));
+            RL_TRY(pc->isq.reserve((size_t)n));
+            RL_TRY(pc->sq.reserve((size_t)n));
         }
         for (int i = 0; i < n; ++i) v[i] = 1.0 / s->h_noise[i];
-        RL_HIP(hipMemcpy(pc.inv, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+        RL_HIP(hipMemcpy(pc->inv, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
         for (int i = 0; i < n; ++i) v[i] = 1.0 / std::sqrt(s->h_noise[i]);
-        RL_HIP(hipMemcpy(pc.isq, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+        RL_HIP(hipMemcpy(pc->isq, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
         for (int i = 0; i < n; ++i) v[i] = std::sqrt(s->h_noise[i]);
-        RL_HIP(hipMemcpy(pc.sq, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+        RL_HIP(hipMemcpy(pc->sq, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
         double sl = 0.0;
         for (int i = 0; i < n; ++i) sl += std::log(s->h_noise[i]);
-        pc.sum_log_eps = sl;
-        pc.eps_ver = s->noise_ver;
+        pc->sum_log_eps = sl;
+        pc->eps_ver = s->noise_ver;
     }
-    if (pc.L_cap < (size_t)kp * n) {
-        pc.L_cap = 0;
-        RL_TRY(hz_grow(&pc.L, (size_t)kp * n));
-        pc.L_cap = (size_t)kp * n;
+    RL_TRY(pc->L.reserve((size_t)kp * n));
+    if (!pc->d) {
+        RL_TRY(pc->d.reserve((size_t)n));
+        RL_TRY(pc->row.reserve((size_t)n));
+        RL_TRY(pc->e.reserve((size_t)n));
+        RL_TRY(pc->mark.reserve((size_t)n));
+        RL_TRY(pc->piv.reserve((size_t)RL_PC_MAXRANK));
+        RL_TRY(pc->pivval.reserve((size_t)RL_PC_MAXRANK + 1));
+        RL_TRY(pc->pv.reserve((size_t)RL_PC_NBLK));
+        RL_TRY(pc->pi.reserve((size_t)RL_PC_NBLK));
     }
-    if (!pc.d) {
-        RL_TRY(hz_grow(&pc.d, (size_t)n));
-        RL_TRY(hz_grow(&pc.row, (size_t)n));
-        RL_TRY(hz_grow(&pc.e, (size_t)n));
-        RL_TRY(hz_grow(&pc.mark, (size_t)n));
-        RL_TRY(hz_grow(&pc.piv, (size_t)RL_PC_MAXRANK));
-        RL_TRY(hz_grow(&pc.pivval, (size_t)RL_PC_MAXRANK + 1));
-        RL_TRY(hz_grow(&pc.pv, (size_t)RL_PC_NBLK));
-        RL_TRY(hz_grow(&pc.pi, (size_t)RL_PC_NBLK));
-    }
-    pc.k = k;
-    pc.kp = kp;
-    if (pc.Mt) RL_HIP(hipFree(pc.Mt));
-    if (pc.Mst) RL_HIP(hipFree(pc.Mst));
-    pc.Mt = pc.Mst = nullptr;
-    RL_HIP(hipMalloc((void**)&pc.Mt, (size_t)kp * kp * sizeof(double)));
-    RL_HIP(hipMalloc((void**)&pc.Mst, (size_t)kp * kp * sizeof(double)));
+    pc->k = k;
+    pc->kp = kp;
+    pc->Mt.reset();
+    pc->Mst.reset();
+    RL_TRY(pc->Mt.reserve((size_t)kp * kp));
+    RL_TRY(pc->Mst.reserve((size_t)kp * kp));
     // everything the single-vector products allocate lazily
     RL_TRY(ski_reserve(s, 1));
-    RL_TRY(gridop_prepare(g, 1));
-    for (const SkiTerm& t : s->extra) RL_TRY(gridop_prepare(t.g, 1));
-    RL_HIP(hipMemsetAsync(pc.L, 0, (size_t)kp * n * sizeof(double), st));
-    RL_HIP(hipMemsetAsync(pc.e, 0, (size_t)n * sizeof(double), st));
-    RL_HIP(hipMemsetAsync(pc.mark, 0, (size_t)n * sizeof(int), st));
+    for (const SkiTerm& t : s->terms) RL_TRY(gridop_prepare(t.g, 1));
+    RL_HIP(hipMemsetAsync(pc->L, 0, (size_t)kp * n * sizeof(double), st));
+    RL_HIP(hipMemsetAsync(pc->e, 0, (size_t)n * sizeof(double), st));
+    RL_HIP(hipMemsetAsync(pc->mark, 0, (size_t)n * sizeof(int), st));
     // 1. the diagonal, term by term
     for (int t = 0; t < nterm; ++t) {
         PcTerm pt;
         RL_TRY(pc_term(s, t, &pt));
-        RL_LAUNCH(k_pc_diag, dim3((n + 255) / 256), dim3(256), 0, st, pt, n, g->D, t > 0 ? 1 : 0, pc.d);
+        RL_LAUNCH(k_pc_diag, dim3((n + 255) / 256), dim3(256), 0, st, pt, n, g->D, t > 0 ? 1 : 0, pc->d);
     }
     RL_HIP(hipGetLastError());
     RL_HIP(hipStreamSynchronize(st));
@@ -1612,44 +1513,44 @@ static int pc_ensure(rl_ski* s, bool* ok, const char** why) {
     // 2. k steps, no host synchronisation between them (the pivot stays on the device)
     const int nb = std::max(1, std::min(RL_PC_NBLK, (n + 1023) / 1024));
     const size_t red = 256 * (sizeof(double) + sizeof(int));
-    double* d0max = pc.pivval + RL_PC_MAXRANK;
-    RL_LAUNCH(k_pc_argmax, dim3(nb), dim3(256), red, st, (const double*)pc.d, n, pc.pv, pc.pi);
+    double* d0max = pc->pivval + RL_PC_MAXRANK;
+    RL_LAUNCH(k_pc_argmax, dim3(nb), dim3(256), red, st, (const double*)pc->d, n, pc->pv, pc->pi);
     for (int j = 0; j < k; ++j) {
-        RL_LAUNCH(k_pc_pick, dim3(1), dim3(256), red, st, (const double*)pc.pv, (const int*)pc.pi, nb, j, n,
-                  pc.piv, pc.pivval, d0max, pc.e);
-        RL_TRY(ski_mvm_int(s, pc.e, pc.row, 1, st, nullptr, false));
+        RL_LAUNCH(k_pc_pick, dim3(1), dim3(256), red, st, (const double*)pc->pv, (const int*)pc->pi, nb, j, n,
+                  pc->piv, pc->pivval, d0max, pc->e);
+        RL_TRY(ski_mvm_int(s, pc->e, pc->row, 1, st, nullptr, false));
         RL_LAUNCH(k_pc_step, dim3(nb), dim3(256), RL_PC_MAXRANK * sizeof(double) + red, st, j,
-                  (const double*)pc.row, pc.L, n, (const int*)pc.piv, (const double*)pc.pivval,
-                  (const double*)d0max, pc.rel_tol, pc.d, pc.mark, pc.pv, pc.pi);
+                  (const double*)pc->row, pc->L, n, (const int*)pc->piv, (const double*)pc->pivval,
+                  (const double*)d0max, pc->rel_tol, pc->d, pc->mark, pc->pv, pc->pi);
     }
     RL_HIP(hipGetLastError());
-    pc.h_piv.assign(k, 0);
-    pc.h_pivval.assign(k, 0.0);
+    pc->h_piv.assign(k, 0);
+    pc->h_pivval.assign(k, 0.0);
     double h_d0 = 0.0;
-    RL_HIP(hipMemcpyAsync(pc.h_piv.data(), pc.piv, (size_t)k * sizeof(int), hipMemcpyDeviceToHost, st));
-    RL_HIP(hipMemcpyAsync(pc.h_pivval.data(), pc.pivval, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
+    RL_HIP(hipMemcpyAsync(pc->h_piv.data(), pc->piv, (size_t)k * sizeof(int), hipMemcpyDeviceToHost, st));
+    RL_HIP(hipMemcpyAsync(pc->h_pivval.data(), pc->pivval, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, st));
     RL_HIP(hipMemcpyAsync(&h_d0, d0max, sizeof(double), hipMemcpyDeviceToHost, st));
     RL_HIP(hipStreamSynchronize(st));
     const auto t_steps = clk::now();
     int r = k;
     for (int j = 0; j < k; ++j)
-        if (!(pc.h_pivval[j] > pc.rel_tol * h_d0) || !(pc.h_pivval[j] > 0.0)) { r = j; break; }
+        if (!(pc->h_pivval[j] > pc->rel_tol * h_d0) || !(pc->h_pivval[j] > 0.0)) { r = j; break; }
     if (r == 0) {
         *why = "pivoted-Cholesky preconditioner: the kernel part of the operator has no positive diagonal entry";
         return RL_OK;
     }
     // 3. H = L^T E^-1 L: the projection of L's own columns (a batch of kp vectors), chunks summed in order
     RL_TRY(pc_reserve(s, kp));
-    pc_project(s, pc.L, pc.inv, kp, st);
+    pc_project(s, pc->L, pc->inv, kp, st);
     {
         const int rows = pc_chunk_rows(n), nchunk = (n + rows - 1) / rows;
         const size_t total = (size_t)kp * kp;
-        RL_LAUNCH(k_pc_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)pc.part,
-                  nchunk, total, pc.cT);       // (cT holds kp * nvp >= kp * kp doubles here)
+        RL_LAUNCH(k_pc_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const double*)pc->part,
+                  nchunk, total, pc->cT);       // (cT holds kp * nvp >= kp * kp doubles here)
     }
     RL_HIP(hipGetLastError());
     std::vector<double> H((size_t)kp * kp);
-    RL_HIP(hipMemcpyAsync(H.data(), pc.cT, H.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    RL_HIP(hipMemcpyAsync(H.data(), pc->cT, H.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     RL_HIP(hipStreamSynchronize(st));
     // host: symmetrised leading blocks; the sample map's Cholesky of H decides the rank that holds
     auto lead = [&](int rr, double add) {
@@ -1699,8 +1600,8 @@ static int pc_ensure(rl_ski* s, bool* ok, const char** why) {
             for (int q = i; q < r; ++q) sacc += Rl[(size_t)q * r + i] * Rl[(size_t)q * r + j];
             C2[(size_t)i * r + j] = C2[(size_t)j * r + i] = sacc;
         }
-    pc.sample_ok = dz_chol(C2, r);
-    if (pc.sample_ok) {
+    pc->sample_ok = dz_chol(C2, r);
+    if (pc->sample_ok) {
         lower(C2, r);
         for (int i = 0; i < r; ++i) C2[(size_t)i * r + i] -= 1.0;
         std::vector<double> T((size_t)r * r, 0.0);       // T = (C2 - I) Ri (lower times lower)
@@ -1719,20 +1620,20 @@ static int pc_ensure(rl_ski* s, bool* ok, const char** why) {
     }
     for (double v : Mt)
         if (!std::isfinite(v)) { *why = "pivoted-Cholesky preconditioner: the solve map is not finite"; return RL_OK; }
-    RL_HIP(hipMemcpy(pc.Mt, Mt.data(), Mt.size() * sizeof(double), hipMemcpyHostToDevice));
-    RL_HIP(hipMemcpy(pc.Mst, Mst.data(), Mst.size() * sizeof(double), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(pc->Mt, Mt.data(), Mt.size() * sizeof(double), hipMemcpyHostToDevice));
+    RL_HIP(hipMemcpy(pc->Mst, Mst.data(), Mst.size() * sizeof(double), hipMemcpyHostToDevice));
     const auto t_end = clk::now();
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    pc.build_ms[0] = ms(t_start, t_diag);
-    pc.build_ms[1] = ms(t_diag, t_steps);
-    pc.build_ms[2] = 0.0;
-    pc.build_ms[3] = ms(t_steps, t_end);
-    pc.rank_used = r;
-    pc.logdet = pc.sum_log_eps + 2.0 * ld;
-    pc.cond = (cmax / cmin) * (cmax / cmin);
-    pc.param_sum = psum;
-    pc.noise_ver = s->noise_ver;
-    pc.valid = true;
+    pc->build_ms[0] = ms(t_start, t_diag);
+    pc->build_ms[1] = ms(t_diag, t_steps);
+    pc->build_ms[2] = 0.0;
+    pc->build_ms[3] = ms(t_steps, t_end);
+    pc->rank_used = r;
+    pc->logdet = pc->sum_log_eps + 2.0 * ld;
+    pc->cond = (cmax / cmin) * (cmax / cmin);
+    pc->param_sum = psum;
+    pc->noise_ver = s->noise_ver;
+    pc->valid = true;
     *ok = true;
     return RL_OK;
 }
@@ -1745,13 +1646,13 @@ static int dz_available(rl_ski* s, bool* ok, const char** why) {
     *ok = false;
     *why = "";
     if (g->lead) { *why = "3-D grid: no polynomial form and no factorisation on a three-dimensional grid"; return RL_OK; }
-    if (!s->extra.empty()) { *why = "kernels on several grids"; return RL_OK; }
+    if (!single_term(s)) { *why = "kernels on several grids"; return RL_OK; }
     if (g->wide) {
         *why = g->D > RL_MAX_D ? "more than 16 outputs"
                                : "2-D grid whose rows of D outputs exceed the LDS row tile";
         return RL_OK;
     }
-    if (s->W4_base == nullptr || s->h_base.empty() || s->ngrid != g->D * g->m) {
+    if (s->terms[0].W4_base == nullptr || s->terms[0].h_base.empty() || s->ngrid != g->D * g->m) {
         *why = "W is not a cubic interpolant of a 1-D grid"; return RL_OK;
     }
     if (!g->lr_try || g->kn.no_rp || (s->kn.rp_fly & 2)) { *why = "polynomial form switched off or grid not eligible"; return RL_OK; }
@@ -1872,7 +1773,7 @@ static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
         if (!s->dz_eps_why) {
             std::vector<double> inv((size_t)n);
             for (int i = 0; i < n; ++i) inv[i] = 1.0 / s->h_noise[i];
-            if (!s->dz_inv) RL_HIP(hipMalloc((void**)&s->dz_inv, (size_t)n * sizeof(double)));
+            RL_TRY(s->dz_inv.reserve((size_t)n));
             RL_HIP(hipMemcpy(s->dz_inv, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice));
         }
         s->dz_eps_ver = s->noise_ver;
@@ -1928,13 +1829,7 @@ static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
     RL_TRY(dz_upload_sample_map(s, Zh));
     for (double v : Zs)
         if (!std::isfinite(v)) { *why = "the solve map is not finite"; return RL_OK; }
-    if (s->dz_Zt_cap < Zs.size()) {
-        if (s->dz_Zt) RL_HIP(hipFree(s->dz_Zt));
-        s->dz_Zt = nullptr;
-        s->dz_Zt_cap = 0;
-        RL_HIP(hipMalloc((void**)&s->dz_Zt, Zs.size() * sizeof(double)));
-        s->dz_Zt_cap = Zs.size();
-    }
+    RL_TRY(s->dz_Zt.reserve(Zs.size()));
     RL_HIP(hipMemcpy(s->dz_Zt, Zs.data(), Zs.size() * sizeof(double), hipMemcpyHostToDevice));
     s->dz_logdet = logdet;
     s->dz_cond = (pmax / pmin) * (pmax / pmin);
@@ -2068,22 +1963,19 @@ extern "C" int rl_solve_direct(rl_ski* s, const double* B, double* X, int nrhs, 
     RL_TRY(ski_reserve_perm(s, nrhs));
     const size_t ve = (size_t)nrhs * n;
     if (s->dz_vec_cap < ve) {
-        if (s->dz_res) RL_HIP(hipFree(s->dz_res));
-        if (s->dz_cor) RL_HIP(hipFree(s->dz_cor));
-        s->dz_res = s->dz_cor = nullptr;
+        s->dz_res.reset();
+        s->dz_cor.reset();
         s->dz_vec_cap = 0;
-        RL_HIP(hipMalloc((void**)&s->dz_res, ve * sizeof(double)));
-        RL_HIP(hipMalloc((void**)&s->dz_cor, ve * sizeof(double)));
+        RL_TRY(s->dz_res.reserve(ve));
+        RL_TRY(s->dz_cor.reserve(ve));
         s->dz_vec_cap = ve;
     }
     if (s->dz_rhs_cap < (size_t)nrhs) {
-        if (s->dz_part) RL_HIP(hipFree(s->dz_part));
-        if (s->dz_go) RL_HIP(hipFree(s->dz_go));
-        s->dz_part = nullptr;
-        s->dz_go = nullptr;
+        s->dz_part.reset();
+        s->dz_go.reset();
         s->dz_rhs_cap = 0;
-        RL_HIP(hipMalloc((void**)&s->dz_part, (size_t)nrhs * (2 * RL_DZ_NBLK + 1) * sizeof(double)));
-        RL_HIP(hipMalloc((void**)&s->dz_go, (size_t)nrhs * sizeof(int)));
+        RL_TRY(s->dz_part.reserve((size_t)nrhs * (2 * RL_DZ_NBLK + 1)));
+        RL_TRY(s->dz_go.reserve((size_t)nrhs));
         s->dz_rhs_cap = (size_t)nrhs;
     }
     const double* Bi = B;
@@ -2221,62 +2113,46 @@ static int pcg_core(rl_ski* s, const double* B, double* X, int nrhs, double tol,
     if (record) {
         maxiter = std::min(maxiter, cap);
         const size_t need = (size_t)cap * nrhs * 2;
-        if (s->dz_rec_cap < need) {
-            s->dz_rec_cap = 0;
-            RL_TRY(hz_grow(&s->dz_rec, need));
-            s->dz_rec_cap = need;
-        }
+        RL_TRY(s->dz_rec.reserve(need));
     }
     // (mode 4 has none of the polynomial form's tables: a 3-D or wide handle could not build them)
     const bool pcm = s->pc.active;
     if (!pcm) RL_TRY(rp_prepare(s, std::max(nrhs, R)));
     RL_TRY(ski_reserve(s, nrhs));
-    RL_TRY(gridop_prepare(g, nrhs));
-    if (pcm)
-        for (const SkiTerm& t : s->extra) RL_TRY(gridop_prepare(t.g, nrhs));
+    for (size_t t = 0; t < (pcm ? s->terms.size() : 1); ++t) RL_TRY(gridop_prepare(s->terms[t].g, nrhs));
     if (rp_ok(s, nrhs)) RL_TRY(rp_prepare(s, nrhs));
     RL_TRY(ski_reserve_perm(s, nrhs));
     if (pcm) RL_TRY(pc_reserve(s, nrhs));
     else if (s->dz_hz) RL_TRY(hz_reserve(s, nrhs));
     const size_t ve = (size_t)nrhs * n;
     if (s->dz_vec_cap < ve) {
-        if (s->dz_res) RL_HIP(hipFree(s->dz_res));
-        if (s->dz_cor) RL_HIP(hipFree(s->dz_cor));
-        s->dz_res = s->dz_cor = nullptr;
+        s->dz_res.reset();
+        s->dz_cor.reset();
         s->dz_vec_cap = 0;
-        RL_HIP(hipMalloc((void**)&s->dz_res, ve * sizeof(double)));
-        RL_HIP(hipMalloc((void**)&s->dz_cor, ve * sizeof(double)));
+        RL_TRY(s->dz_res.reserve(ve));
+        RL_TRY(s->dz_cor.reserve(ve));
         s->dz_vec_cap = ve;
     }
     if (s->dz_pq_cap < ve) {
-        if (s->dz_p) RL_HIP(hipFree(s->dz_p));
-        if (s->dz_q) RL_HIP(hipFree(s->dz_q));
-        s->dz_p = s->dz_q = nullptr;
+        s->dz_p.reset();
+        s->dz_q.reset();
         s->dz_pq_cap = 0;
-        RL_HIP(hipMalloc((void**)&s->dz_p, ve * sizeof(double)));
-        RL_HIP(hipMalloc((void**)&s->dz_q, ve * sizeof(double)));
+        RL_TRY(s->dz_p.reserve(ve));
+        RL_TRY(s->dz_q.reserve(ve));
         s->dz_pq_cap = ve;
     }
     if (s->dz_rhs_cap < (size_t)nrhs) {
-        if (s->dz_part) RL_HIP(hipFree(s->dz_part));
-        if (s->dz_go) RL_HIP(hipFree(s->dz_go));
-        s->dz_part = nullptr;
-        s->dz_go = nullptr;
+        s->dz_part.reset();
+        s->dz_go.reset();
         s->dz_rhs_cap = 0;
-        RL_HIP(hipMalloc((void**)&s->dz_part, (size_t)nrhs * (2 * RL_DZ_NBLK + 1) * sizeof(double)));
-        RL_HIP(hipMalloc((void**)&s->dz_go, (size_t)nrhs * sizeof(int)));
+        RL_TRY(s->dz_part.reserve((size_t)nrhs * (2 * RL_DZ_NBLK + 1)));
+        RL_TRY(s->dz_go.reserve((size_t)nrhs));
         s->dz_rhs_cap = (size_t)nrhs;
     }
     // (dz_scal under a capacity of its own: dz_part / dz_go are shared with rl_solve_direct, which
     // grows them -- and dz_rhs_cap -- without it.  Sized by dz_rhs_cap, a handle that ran PCG on 3
     // systems, the direct solver on 39 and PCG on 21 wrote 21 pairs into room for 3)
-    if (s->dz_scal_cap < (size_t)nrhs) {
-        if (s->dz_scal) RL_HIP(hipFree(s->dz_scal));
-        s->dz_scal = nullptr;
-        s->dz_scal_cap = 0;
-        RL_HIP(hipMalloc((void**)&s->dz_scal, (size_t)nrhs * 2 * sizeof(double)));
-        s->dz_scal_cap = (size_t)nrhs;
-    }
+    RL_TRY(s->dz_scal.reserve((size_t)nrhs * 2));
     const double* Bi = B;
     double* Xi = X;
     if (s->permuted) {
@@ -2466,7 +2342,7 @@ extern "C" int rl_ski_precond_sample(rl_ski* s, const double* Win, double* Rout,
     if (s->dz_isq_ver != s->noise_ver || s->dz_isq == nullptr) {
         std::vector<double> isq((size_t)n);
         for (int i = 0; i < n; ++i) isq[i] = 1.0 / std::sqrt(s->h_noise[i]);
-        if (!s->dz_isq) RL_HIP(hipMalloc((void**)&s->dz_isq, (size_t)n * sizeof(double)));
+        RL_TRY(s->dz_isq.reserve((size_t)n));
         RL_HIP(hipMemcpy(s->dz_isq, isq.data(), isq.size() * sizeof(double), hipMemcpyHostToDevice));
         s->dz_isq_ver = s->noise_ver;
     }
@@ -2483,11 +2359,7 @@ extern "C" int rl_ski_precond_sample(rl_ski* s, const double* Win, double* Rout,
     }
     // in = w / sqrt(eps), in a buffer of its own (the apply functions do not alias in and out)
     const size_t ve = (size_t)nvec * n;
-    if (s->dz_smp_cap < ve) {
-        s->dz_smp_cap = 0;
-        RL_TRY(hz_grow(&s->dz_smp, ve));
-        s->dz_smp_cap = ve;
-    }
+    RL_TRY(s->dz_smp.reserve(ve));
     const int nblk = std::max(1, std::min(RL_DZ_NBLK, (n + 1023) / 1024));
     RL_LAUNCH(k_dz_scale, dim3(nblk, nvec), dim3(256), 0, st, Wi, (const double*)s->dz_isq, n, s->dz_smp);
     RL_TRY(dz_apply(s, s->dz_smp, Ri, nvec, st, (const double*)s->dz_Zh, (const double*)s->noise_diag));
@@ -2598,17 +2470,17 @@ extern "C" int rl_ski_pivchol_info(rl_ski* s, int* rank_used, int* pivots, doubl
                                    double* resid_diag_dev) {
     if (!s) return fail(RL_EINVAL, "rl_ski_pivchol_info: NULL handle");
     RL_TRY(pc_current(s, "rl_ski_pivchol_info"));
-    const PcState& pc = s->pc;
-    if (rank_used) *rank_used = pc.rank_used;
+    const PcState* pc = &s->pc;
+    if (rank_used) *rank_used = pc->rank_used;
     // (pivots in the CALLER's row numbering)
-    for (int j = 0; j < pc.k; ++j) {
-        if (pivots) pivots[j] = s->permuted ? s->h_perm[pc.h_piv[j]] : pc.h_piv[j];
-        if (pivot_values) pivot_values[j] = pc.h_pivval[j];
+    for (int j = 0; j < pc->k; ++j) {
+        if (pivots) pivots[j] = s->permuted ? s->h_perm[pc->h_piv[j]] : pc->h_piv[j];
+        if (pivot_values) pivot_values[j] = pc->h_pivval[j];
     }
     if (resid_diag_dev) {
         RL_HIP(hipSetDevice(s->g->device));
         RL_LAUNCH(k_pc_unpermute, dim3((s->n + 255) / 256, 1), dim3(256), 0, (hipStream_t) nullptr,
-                  (const double*)pc.d, s->permuted ? (const int*)s->perm : (const int*)nullptr, s->n,
+                  (const double*)pc->d, s->permuted ? (const int*)s->perm : (const int*)nullptr, s->n,
                   resid_diag_dev);
         RL_HIP(hipGetLastError());
         RL_HIP(hipDeviceSynchronize());
@@ -2619,10 +2491,10 @@ extern "C" int rl_ski_pivchol_info(rl_ski* s, int* rank_used, int* pivots, doubl
 extern "C" int rl_ski_pivchol_factor(rl_ski* s, double* L_dev) {
     if (!s || !L_dev) return fail(RL_EINVAL, "rl_ski_pivchol_factor: NULL argument");
     RL_TRY(pc_current(s, "rl_ski_pivchol_factor"));
-    const PcState& pc = s->pc;
+    const PcState* pc = &s->pc;
     RL_HIP(hipSetDevice(s->g->device));
-    RL_LAUNCH(k_pc_unpermute, dim3((s->n + 255) / 256, pc.rank_used), dim3(256), 0, (hipStream_t) nullptr,
-              (const double*)pc.L, s->permuted ? (const int*)s->perm : (const int*)nullptr, s->n, L_dev);
+    RL_LAUNCH(k_pc_unpermute, dim3((s->n + 255) / 256, pc->rank_used), dim3(256), 0, (hipStream_t) nullptr,
+              (const double*)pc->L, s->permuted ? (const int*)s->perm : (const int*)nullptr, s->n, L_dev);
     RL_HIP(hipGetLastError());
     RL_HIP(hipDeviceSynchronize());
     return RL_OK;
