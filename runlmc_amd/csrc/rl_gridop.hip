@@ -114,7 +114,6 @@ RlKnobs read_knobs() {
     k.precond_hi_min = num("RUNLMC_PRECOND_HI_MIN", 100000);
     k.precond_hi_rank = (int)num("RUNLMC_PRECOND_HI_RANK", 192);
     k.precond_hi_use = (int)num("RUNLMC_PRECOND_HI_USE", 0);
-    k.rp_fly = (int)num("RUNLMC_RP_FLY", 1);
     k.no_rp_small = flag("RUNLMC_NO_RP_SMALL");
     k.no_rp_fuse = flag("RUNLMC_NO_RP_FUSE");
     k.rp_pfuse = !flag("RUNLMC_NO_RP_PFUSE");
@@ -950,8 +949,8 @@ static std::vector<double> lead_rows(const rl_gridop* g, int Q, const double* to
 
 // ... and every child set with its Q rows and the caller's couplings, unchanged.  A failure
 // leaves the handle without parameters.
-static int lead_set(rl_gridop* g, int Q, const double* tops,
-                    const std::function<int(rl_gridop*, const double*)>& set_child) {
+template <class SetChild>      // int set_child(rl_gridop* child, const double* rows)
+static int lead_set(rl_gridop* g, int Q, const double* tops, const SetChild& set_child) {
     g->Q = 0;
     ++g->param_ver;
     const std::vector<double> rows = lead_rows(g, Q, tops);
@@ -1554,9 +1553,8 @@ static void lr_expand(rl_gridop* g, const double* zhat, int nrows, double* Y, in
 }
 template <int R>
 static void lr_launch(rl_gridop* g, const double* X, double* Y, int nvec, int Q, const double* Cq,
-                      const double* Bq, hipStream_t st, int accumulate = 0) {
+                      const double* Bq, hipStream_t st, int accumulate = 0, bool deferred = false) {
     const int nrows = nvec * g->D;
-    const bool deferred = g->defer_expand && !accumulate && R <= g->kn.w_poly_rmax;
     // (Measured and dropped, round 5: a large batch as TWO half batches, the second one a
     // projection behind on a side stream, so that the first half's expansion writes while the
     // second half's projection reads -- the box copies the step's vectors at 5.2-5.8 TB/s where
@@ -1567,26 +1565,22 @@ static void lr_launch(rl_gridop* g, const double* X, double* Y, int nvec, int Q,
     // follows as a launch of its own -- not a solver round's, whose x the previous kernel wrote)
     const int chunks = lr_project<R>(g, X, nrows, st, nullptr, !accumulate && !deferred);
     lr_mix<R>(g, g->lr_part, chunks, nvec, Q, Cq, Bq, g->lr_zhat, st);
-    // (ski_mvm_int: the W kernel expands, k_spmv_w_poly -- ranks 24 and 32 only: at rank 48
-    // the evaluation costs more than the two vector passes it saves -- measured, C5
-    // periodic: 5.03 against 4.17 ms per solver round)
-    if (deferred) {
-        g->expand_deferred = true;
-        return;
-    }
+    // (ski_mvm_int: the W kernel expands, k_spmv_w_poly: grid_route's `deferrable`)
+    if (deferred) return;
     lr_expand<R>(g, g->lr_zhat, nrows, Y, accumulate, st);
 }
 
 // Y = Phi [sum_q B_q (x) C_q] Phi^T X for tops [q0, q0 + Q) with coupling Bq
+// (deferred: stop after the mix -- the caller's W kernel expands lr_zhat itself)
 static int lr_apply(rl_gridop* g, const double* X, double* Y, int nvec, int q0, int Q,
-                    const double* Bq, hipStream_t st) {
+                    const double* Bq, hipStream_t st, bool deferred = false) {
     const double* Cq = g->lr_C + (size_t)q0 * g->lr_r * g->lr_r;
     switch (g->lr_r) {
-        case 24: lr_launch<24>(g, X, Y, nvec, Q, Cq, Bq, st); break;
-        case 32: lr_launch<32>(g, X, Y, nvec, Q, Cq, Bq, st); break;
-        case 36: lr_launch<36>(g, X, Y, nvec, Q, Cq, Bq, st); break;
-        case 40: lr_launch<40>(g, X, Y, nvec, Q, Cq, Bq, st); break;
-        case 48: lr_launch<48>(g, X, Y, nvec, Q, Cq, Bq, st); break;
+        case 24: lr_launch<24>(g, X, Y, nvec, Q, Cq, Bq, st, 0, deferred); break;
+        case 32: lr_launch<32>(g, X, Y, nvec, Q, Cq, Bq, st, 0, deferred); break;
+        case 36: lr_launch<36>(g, X, Y, nvec, Q, Cq, Bq, st, 0, deferred); break;
+        case 40: lr_launch<40>(g, X, Y, nvec, Q, Cq, Bq, st, 0, deferred); break;
+        case 48: lr_launch<48>(g, X, Y, nvec, Q, Cq, Bq, st, 0, deferred); break;
         default: return fail(RL_EINVAL, "low-rank path: bad basis size");
     }
     RL_HIP(hipGetLastError());
@@ -1610,7 +1604,8 @@ static int lr_apply_compact(rl_gridop* g, const double* X, double* Y, int nvec, 
 }
 
 static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, double* Y, int nvec,
-                        hipStream_t stream);
+                        hipStream_t stream, bool allow_deferred_expand = false,
+                        bool* expansion_deferred = nullptr);
 
 // ---------------------------------------------------------------------------
 // recursive-filter form (rl_filter.h): detection of exponential-polynomial top
@@ -1762,16 +1757,6 @@ static size_t sf_need_E(const rl_gridop* g, int nvec, int NF, int NS) {
 }
 static size_t sf_need_Cin(const rl_gridop* g, int nvec, int nchan, int NS) {
     return (size_t)sf_nchunks(g) * nvec * nchan * 2 * NS;
-}
-static bool sf_ready(const rl_gridop* g, int nvec, int NF, int nfac, int NS) {
-    return g->sf_E.cap >= sf_need_E(g, nvec, NF, NS) &&
-           g->sf_Cin.cap >= sf_need_Cin(g, nvec, g->D * NF + nfac, NS);
-}
-static int sf_reserve(rl_gridop* g, int nvec, int NF, int nfac, int NS) {
-    const size_t needE = sf_need_E(g, nvec, NF, NS), needC = sf_need_Cin(g, nvec, g->D * NF + nfac, NS);
-    RL_TRY(g->sf_E.reserve(needE));
-    RL_TRY(g->sf_Cin.reserve(needC));
-    return RL_OK;
 }
 // (NS: states per direction; two-state launches keep the three-state size)
 static size_t sf_apply_lds(int D, int nfac, int NF, int nthr, int NS) {
@@ -2457,13 +2442,79 @@ static int forms_setup(rl_gridop* g, const std::vector<double>& A, const std::ve
     return RL_OK;
 }
 
+// The route of a grid product (rl_host.h GridRoute).  Does a structured form apply to the batch
+// at all?  Above the batch gate every top row runs in the form it was found in at set time; below
+// it an operator wholly in the polynomial form has the small-batch kernels -- all rows only, on a
+// handle whose gate was not moved (rl_gridop_set_form_gate: it keeps to what the caller asked for)
+enum GridGate { GATE_NONE, GATE_BIG, GATE_SMALL };
+static GridGate grid_gate(const rl_gridop* g, int q, int nvec) {
+    if (g->lr_bypass) return GATE_NONE;
+    if ((g->lr_try || g->sf_try) && (size_t)nvec * g->D * g->m >= g->lr_min) return GATE_BIG;
+    return g->lr_try && !g->kn.no_lr_small && (size_t)g->D * g->m <= RL_LR_SMALL_MAX &&
+                   g->lr_min == lr_min_elements(g) && q < 0 ? GATE_SMALL : GATE_NONE;
+}
+GridRoute grid_route(const rl_gridop* g, int q, int nvec) {
+    GridRoute r;
+    // short grid, enough pairs to fill the chip with one workgroup per pair
+    // (measured: D=13, m=238: 21 vs 46 us at 256 vectors, 95 vs 228 us at 2048,
+    // but 19.6 vs 16.5 us at 16 -- a few workgroups walking all D transforms
+    // are slower than three launches spread over the chip): one kernel,
+    // nothing through global memory
+    r.fallback = g->v1p && (nvec >= g->v1p_min || g->D <= 2) ? GRID_K1 : GRID_TRANSFORM;
+    r.form = r.fallback;
+    const GridGate gate = grid_gate(g, q, nvec);
+    if (gate == GATE_NONE || g->lr_dirty) return r;
+    if (gate == GATE_SMALL) {
+        if (g->lr_ok && g->lr_Mf_ok && nvec <= 65535) {
+            r.form = GRID_POLY_SMALL;
+            r.lr_spart = (size_t)nvec * g->D * lr_small_nseg(g->m) * RL_LR_RMAX;
+        }
+        return r;
+    }
+    // a batch large enough to fill the chip with projection / filter workgroups:
+    // each top row in the form it was found in at set time (forms_setup)
+    const int form = q >= 0 ? g->top_form[q] : (g->lr_ok ? 1 : (g->st_ok ? 3 : 0));
+    if (form == 0) return r;
+    if (form == 1 || (form == 3 && g->lr_np > 0)) {
+        r.lr_part = lr_part_need(g, nvec);
+        r.lr_zhat = (size_t)nvec * g->D * RL_LR_RMAX;
+    }
+    if (form >= 2) {
+        const int NF = q >= 0 ? 1 : g->sf_n, nfac = q >= 0 ? 0 : g->sf_nfac;
+        const int NS = q >= 0 ? g->sf_top_ns[q] : g->sf_ns;
+        r.sf_E = sf_need_E(g, nvec, NF, NS);
+        r.sf_Cin = sf_need_Cin(g, nvec, g->D * NF + nfac, NS);
+    }
+    r.form = form == 1 ? GRID_POLY : (form == 2 ? GRID_FILTER : GRID_FILTER_POLY);
+    // (the W kernel expands, k_spmv_w_poly -- ranks 24 and 32 only: at rank 48
+    // the evaluation costs more than the two vector passes it saves -- measured, C5
+    // periodic: 5.03 against 4.17 ms per solver round)
+    r.deferrable = form == 1 && g->lr_r <= g->kn.w_poly_rmax;
+    return r;
+}
+static bool grid_ready(const rl_gridop* g, const GridRoute& r) {
+    return g->lr_part.cap >= r.lr_part && g->lr_zhat.cap >= r.lr_zhat && g->sf_E.cap >= r.sf_E &&
+           g->sf_Cin.cap >= r.sf_Cin && g->lr_spart.cap >= r.lr_spart;
+}
+static int grid_reserve(rl_gridop* g, const GridRoute& r) {
+    RL_TRY(g->lr_part.reserve(r.lr_part));
+    RL_TRY(g->lr_zhat.reserve(r.lr_zhat));
+    RL_TRY(g->sf_E.reserve(r.sf_E));
+    RL_TRY(g->sf_Cin.reserve(r.sf_Cin));
+    RL_TRY(g->lr_spart.reserve(r.lr_spart));
+    return RL_OK;
+}
+
 // before a capture: pending verification and buffers for batches of nvec vectors
 int lr_prepare(rl_gridop* g, int nvec) {
-    if ((!g->lr_try && !g->sf_try) || (size_t)nvec * g->D * g->m < g->lr_min) return RL_OK;
+    // Kept different from the product on purpose: a single-top product
+    // (rl_gridop_mvm_top) is not prepared, nor is a batch below the gate (verification, lr_spart)
+    const int all_rows_only = -1;
+    const GridGate gate = grid_gate(g, all_rows_only, nvec);
+    const bool small_batch_unprepared = gate == GATE_SMALL;
+    if (gate == GATE_NONE || small_batch_unprepared) return RL_OK;
     RL_TRY(lr_ensure(g));
-    if (g->lr_ok || (g->st_ok && g->lr_np)) RL_TRY(lr_reserve(g, nvec));
-    if (g->st_ok) RL_TRY(sf_reserve(g, nvec, g->sf_n, g->sf_nfac, g->sf_ns));
-    return RL_OK;
+    return grid_reserve(g, grid_route(g, all_rows_only, nvec));
 }
 
 // runs the verification the last parameter update left pending
@@ -2692,8 +2743,10 @@ static int lead_mvm(rl_gridop* g, int q, const double* X, double* Y, int nvec, h
     return RL_OK;
 }
 
+// The entry of the products of a 1-D or 2-D handle (D <= RL_MAX_D): the one place that asks whether
+// the stream is being captured -- at most once, and only when something would be allocated or verified
 static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, double* Y, int nvec,
-                        hipStream_t stream) {
+                        hipStream_t stream, bool allow_deferred_expand, bool* expansion_deferred) {
     if (!g) return fail(RL_EINVAL, "gridop is NULL");
     if (nvec < 0) return fail(RL_EINVAL, "nvec < 0");
     if (nvec == 0) return RL_OK;
@@ -2701,69 +2754,38 @@ static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, doub
     if (X == Y) return fail(RL_EINVAL, "X and Y may not alias");
     if (g->Q < 1) return fail(RL_EINVAL, "grid operator has no parameters yet");
     RL_HIP(hipSetDevice(g->device));
-    const bool big = (g->lr_try || g->sf_try) && !g->lr_bypass &&
-                     (size_t)nvec * g->D * g->m >= g->lr_min;
+    int asked = -1;         // (not yet)
+    auto capturing = [&] { return (asked < 0 ? asked = stream_capturing(stream) : asked) != 0; };
+    const bool single = mp.nfac == 0 && mp.Q == 1 && mp.kappa == g->ones;
+    const int q1 = single ? (int)((mp.spec - g->spec) / g->L) : -1;
     // (nothing may be allocated or copied inside a capture: a pending verification
     // waits for the next product outside one; the solver runs it before it captures)
-    const bool capturing = big && stream_capturing(stream);
-    if (big && g->lr_dirty && !capturing) {
-        // (the verification runs whole products of its own: never with a deferred expansion)
-        const bool defer = g->defer_expand;
-        g->defer_expand = false;
-        const int rc = lr_ensure(g);
-        g->defer_expand = defer;
-        if (rc != RL_OK) return rc;
+    if (g->lr_dirty && grid_gate(g, q1, nvec) != GATE_NONE && !capturing()) RL_TRY(lr_ensure(g));
+    GridRoute route = grid_route(g, q1, nvec);
+    if (route.form != route.fallback && !grid_ready(g, route)) {
+        if (capturing()) route.form = route.fallback;
+        else RL_TRY(grid_reserve(g, route));
     }
-    if (big && !g->lr_dirty) {
-        // a batch large enough to fill the chip with projection / filter workgroups:
-        // each top row in the form it was found in at set time (forms_setup)
-        const bool single = mp.nfac == 0 && mp.Q == 1 && mp.kappa == g->ones;
-        const int q1 = single ? (int)((mp.spec - g->spec) / g->L) : -1;
-        const int form = single ? g->top_form[q1] : (g->lr_ok ? 1 : (g->st_ok ? 3 : 0));
-        const bool poly_part = form == 1 || (form == 3 && g->lr_np > 0);
-        bool ready = true;
-        if (poly_part)
-            ready = g->lr_part.cap >= lr_part_need(g, nvec) &&
-                    g->lr_zhat.cap >= (size_t)nvec * g->D * RL_LR_RMAX;
-        const int sNF = single ? 1 : g->sf_n, sfac = single ? 0 : g->sf_nfac;
-        const int sNS = single ? (form == 2 ? g->sf_top_ns[q1] : 2) : g->sf_ns;
-        if (form >= 2) ready = ready && sf_ready(g, nvec, sNF, sfac, sNS);
-        if (form != 0 && !ready && !capturing) {
-            if (poly_part) RL_TRY(lr_reserve(g, nvec));
-            if (form >= 2) RL_TRY(sf_reserve(g, nvec, sNF, sfac, sNS));
-            ready = true;
+    switch (route.form) {
+        case GRID_POLY: {
+            trace_once("grid product: polynomial-subspace form (k_lr_project / mix / expand)");
+            const bool deferred = allow_deferred_expand && route.deferrable;
+            if (expansion_deferred) *expansion_deferred = deferred;
+            if (single) return lr_apply(g, X, Y, nvec, q1, 1, g->lr_eye, stream, deferred);
+            return lr_apply(g, X, Y, nvec, 0, g->Q, g->lr_B, stream, deferred);
         }
-        if (form != 0 && ready) {
-            if (form == 1) {
-                trace_once("grid product: polynomial-subspace form (k_lr_project / mix / expand)");
-                if (single) return lr_apply(g, X, Y, nvec, q1, 1, g->lr_eye, stream);
-                return lr_apply(g, X, Y, nvec, 0, g->Q, g->lr_B, stream);
-            }
-            if (form == 2) {
-                trace_once("grid product: recursive-filter form (k_sf_carries / scan / apply)");
-                return sf_apply_top(g, q1, X, Y, nvec, stream);
-            }
+        case GRID_FILTER:
+            trace_once("grid product: recursive-filter form (k_sf_carries / scan / apply)");
+            return sf_apply_top(g, q1, X, Y, nvec, stream);
+        case GRID_FILTER_POLY:
             trace_once("grid product: recursive-filter part + polynomial part");
             RL_TRY(sf_apply_all(g, X, Y, nvec, stream));
             if (g->lr_np > 0) RL_TRY(lr_apply_compact(g, X, Y, nvec, stream));
             return RL_OK;
-        }
-    }
-    // A small batch (below the gate) of an operator that IS wholly in the polynomial form: two
-    // launches spread over the chip (k_lr_small_project / k_lr_small_expand, rl_lowrank.h).  The pending verification of
-    // the form runs for such a batch too when the grid could take this path (outside captures;
-    // back-off after rejections as for big batches); a handle whose gate was moved
-    // (rl_gridop_set_form_gate) keeps to what the caller asked for.
-    const bool small_try = !big && g->lr_try && !g->lr_bypass && !g->kn.no_lr_small &&
-                           (size_t)g->D * g->m <= RL_LR_SMALL_MAX && g->lr_min == lr_min_elements(g) &&
-                           !(mp.nfac == 0 && mp.Q == 1 && mp.kappa == g->ones);
-    if (small_try && g->lr_dirty && !stream_capturing(stream)) RL_TRY(lr_ensure(g));
-    if (small_try && !g->lr_dirty && g->lr_ok && g->lr_Mf_ok && nvec <= 65535) {
-        const int nseg = lr_small_nseg(g->m);
-        const size_t need = (size_t)nvec * g->D * nseg * RL_LR_RMAX;
-        if (g->lr_spart.cap < need && !stream_capturing(stream)) RL_TRY(g->lr_spart.reserve(need));
-        if (g->lr_spart.cap >= need) {
+        case GRID_POLY_SMALL: {
+            // two launches spread over the chip (k_lr_small_project / k_lr_small_expand, rl_lowrank.h)
             trace_once("grid product: polynomial-subspace form, small batch (k_lr_small_project / k_lr_small_expand)");
+            const int nseg = lr_small_nseg(g->m);
             const dim3 grid(g->D * nseg, nvec), blk(RL_LR_SMALL_WG);
 #define RL_LR_SMALL(R_)                                                                           \
             RL_LAUNCH(k_lr_small_project<R_>, grid, blk, lr_small_project_lds(R_), stream, X, g->D, g->m, nseg, \
@@ -2782,20 +2804,16 @@ static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, doub
             RL_HIP(hipGetLastError());
             return RL_OK;
         }
-    }
-    if (g->v1p && (nvec >= g->v1p_min || g->D <= 2)) {
-        // short grid, enough pairs to fill the chip with one workgroup per pair
-        // (measured: D=13, m=238: 21 vs 46 us at 256 vectors, 95 vs 228 us at 2048,
-        // but 19.6 vs 16.5 us at 16 -- a few workgroups walking all D transforms
-        // are slower than three launches spread over the chip): one kernel,
-        // nothing through global memory
-        trace_once("grid product: k1_product (single tile)");
-        MixParams mp1 = mp;
-        mp1.spec = g->spec1 + (mp.spec - g->spec);
-        RL_TRY(launch1p(g, g->D, (unsigned)(((size_t)nvec + 1) / 2), stream, X, Y, nvec, 0, mp1,
-                        nullptr));
-        RL_HIP(hipGetLastError());
-        return RL_OK;
+        case GRID_K1: {
+            trace_once("grid product: k1_product (single tile)");
+            MixParams mp1 = mp;
+            mp1.spec = g->spec1 + (mp.spec - g->spec);
+            RL_TRY(launch1p(g, g->D, (unsigned)(((size_t)nvec + 1) / 2), stream, X, Y, nvec, 0, mp1,
+                            nullptr));
+            RL_HIP(hipGetLastError());
+            return RL_OK;
+        }
+        case GRID_TRANSFORM: break;
     }
     const size_t total_pairs = ((size_t)nvec + 1) / 2;
     size_t chunk = std::min(total_pairs, g->chunk_pairs);
@@ -2808,13 +2826,9 @@ static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, doub
     // when chunks hold hundreds of pairs -- C2, 2.51 -> 2.32 M MVM/s)
     const bool want_two = wants_two_streams(g);
     if (g->v2 && total_pairs > chunk && want_two) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = stream != nullptr &&
-                               hipStreamIsCapturing(stream, &cs) == hipSuccess &&
-                               cs != hipStreamCaptureStatusNone;
         // inside a capture nothing may be allocated: the solver prepares the
         // second workspace beforehand (prepare_two_streams) or stays on one
-        if (!capturing) RL_TRY(prepare_two_streams(g, chunk));
+        if (!capturing()) RL_TRY(prepare_two_streams(g, chunk));
         if (g->T2_pairs >= chunk && g->nside > 0) {
             RL_HIP(hipEventRecord(g->ev_fork, stream));
             for (int i = 0; i < g->nside; ++i)
@@ -2852,14 +2866,20 @@ static int mvm_with_mix(rl_gridop* g, const MixParams& mp, const double* X, doub
     return RL_OK;
 }
 
-extern "C" int rl_gridop_mvm(rl_gridop* g, const double* X, double* Y, int nvec, void* stream) {
+int gridop_mvm_int(rl_gridop* g, const double* X, double* Y, int nvec, hipStream_t stream,
+                   bool allow_deferred_expand, bool* expansion_deferred) {
+    if (expansion_deferred) *expansion_deferred = false;
     if (!g) return fail(RL_EINVAL, "gridop is NULL");
-    if (g->lead) return lead_mvm(g, -1, X, Y, nvec, (hipStream_t)stream);
-    if (g->wide) return wide_mvm(g, X, Y, nvec, (hipStream_t)stream);
+    if (g->lead) return lead_mvm(g, -1, X, Y, nvec, stream);
+    if (g->wide) return wide_mvm(g, X, Y, nvec, stream);
     MixParams mp{g->Q, g->nfac, g->spec, g->facA, g->facW, g->facQ, g->kappa,
                  g->mixtab_ok ? g->mixtab.get() : nullptr,
                  g->mixtab_ok ? g->mixtab + (size_t)g->D * g->L : nullptr};
-    return mvm_with_mix(g, mp, X, Y, nvec, (hipStream_t)stream);
+    return mvm_with_mix(g, mp, X, Y, nvec, stream, allow_deferred_expand, expansion_deferred);
+}
+
+extern "C" int rl_gridop_mvm(rl_gridop* g, const double* X, double* Y, int nvec, void* stream) {
+    return gridop_mvm_int(g, X, Y, nvec, (hipStream_t)stream, false, nullptr);
 }
 
 extern "C" int rl_gridop_mvm_top(rl_gridop* g, int q, const double* X, double* Y, int nvec,

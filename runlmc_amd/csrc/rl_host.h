@@ -13,7 +13,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -112,10 +111,6 @@ struct RlKnobs {
                                       // kernel (as first built) instead of k_hz_expand_mm's one pass (A/B)
     bool no_precond_hi = false;       // RUNLMC_NO_PRECOND_HI: operators without a polynomial row keep the 48-function
                                       // preconditioner (not the 96-function one of rl_solve.hip: hz_*)
-    int rp_fly = 1;              // RUNLMC_RP_FLY: bit 0: k_rp_expand computes F from the interpolation entries,
-                                 // bit 1: k_rp_project too (otherwise from the table).  Measured (C5, per round):
-                                 // expansion 257 -> 236 us at 129 vectors, 61 -> 42 at 17; projection level at rank
-                                 // 24 (339 vs 347, 95 vs 92), behind at rank 36 (697 vs 610)
     int w_poly_rmax = 32;        // RUNLMC_W_POLY_RMAX: largest rank whose expansion the W kernel takes over
                                  // (36 measured: 791 us against 186 + 473 for expansion + staged W per C5 round)
     bool no_sort = false;        // RUNLMC_NO_SORT: caller's data order inside the SKI handle
@@ -138,7 +133,7 @@ RlKnobs read_knobs();
 // Device memory.  Every device buffer of a handle is a DevBuf member: the handle's
 // destructor frees it, so `delete h` in a destroy function is the whole of freeing.
 // reserve() never over-allocates and keeps no contents; it knows nothing about streams,
-// so callers reserve outside a capture (the stream_capturing checks at the call sites).
+// so a product's entry function reserves outside a capture only (ski_mvm_int, mvm_with_mix).
 // ---------------------------------------------------------------------------
 template <class T>
 struct DevBuf {
@@ -237,8 +232,6 @@ struct rl_gridop {
     DevBuf<double> lead_tw;  // dev [N0 / 2][2]: exp(-2 pi i k / N0)
     DevBuf<double> lead_x, lead_y;   // [F][2][nvec][D][m1 m2] each
     size_t lead_cap = 0;        // vectors they hold
-    bool defer_expand = false;  // ski_mvm_int: leave the expansion to the W kernel (k_spmv_w_poly) ...
-    bool expand_deferred = false;   // ... done: lr_zhat holds the mixed coefficients of the batch
     int lr_rejects = 0;         // consecutive parameter sets with a top the verification rejected
     int lr_skip = 0;            // parameter updates the verification still sits out (back-off:
                                 // 0, 1, 3 ... 31 updates after 1, 2, 3 ... rejections in a row)
@@ -462,19 +455,14 @@ struct rl_ski {
     int rp_R = 0;                   // rank F was built for (0: none)
     DevBuf<double> rp_Fc;        // the same in the CALLER's row order (rl_ski_mvm: no row permutations)
     int rp_Fc_R = 0;
-    DevBuf<int> rp_base_c;       // interpolation entries in the caller's row order (FLY kernels)
+    DevBuf<int> rp_base_c;       // interpolation entries in the caller's row order (k_rp_expand computes F from them)
     DevBuf<double> rp_w4_c;
     DevBuf<int> rp_runs, rp_run_ptr, rp_out_end;
     int rp_nruns = 0;
     DevBuf<double> rp_part;
     DevBuf<double> rp_nrm;       // fused B: [nrhs] coefficients + [nrhs][rp_nruns] partial norms
-    RpFuse rp_fuse{nullptr, nullptr, nullptr};   // set by the solver around ONE operator product
-    // MINRES's P inside the expansion (rl_rowpoly.h RpPFuse): set by the solver around ONE
-    // operator product together with rp_mid, which launches P's scalar head between the
-    // coefficient map and the expansion; rp_pp: the head's coefficients [nrhs][RL_RP_PCW] and
-    // three arrays of [nrhs][ceil(n / 256)] partial sums
-    RpPFuse rp_pfuse{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    std::function<void(hipStream_t)> rp_mid;
+    // MINRES's P inside the expansion or the staged W product (SkiCall::pfuse): the head's
+    // coefficients [nrhs][RL_RP_PCW] and three arrays of [nrhs][ceil(n / 256)] partial sums
     DevBuf<double> rp_pp;
     std::vector<int> eps_end;       // noise in runs: rows [eps_end[k-1], eps_end[k]) carry eps_val[k]
     std::vector<double> eps_val;    // (empty: more than RL_MAX_D runs)
@@ -571,6 +559,46 @@ struct HandleGuard {
 };
 
 // ---------------------------------------------------------------------------
+// Routes: which kernels a product runs and the buffers they need, decided by ONE function per
+// level (const, no HIP call) that the product, the preparation before a capture and the solver's
+// choice of fusions all ask.  Nothing is allocated inside a capture: a level's entry function
+// (mvm_with_mix, ski_mvm_int) asks the stream once, reserves outside a capture and inside one
+// takes the route only if its buffers are there, else the fallback (DESIGN.md sections 6, 11).
+// ---------------------------------------------------------------------------
+enum GridForm { GRID_TRANSFORM, GRID_K1, GRID_POLY, GRID_FILTER /* one top */,
+                GRID_FILTER_POLY /* all rows: filter part + polynomial part */, GRID_POLY_SMALL };
+struct GridRoute {
+    GridForm form = GRID_TRANSFORM;
+    GridForm fallback = GRID_TRANSFORM;     // unverified parameters, or buffers short in a capture
+    bool deferrable = false;                // GRID_POLY: the W kernel may take the expansion over
+    size_t lr_part = 0, lr_zhat = 0, sf_E = 0, sf_Cin = 0, lr_spart = 0;    // elements needed
+};
+GridRoute grid_route(const rl_gridop* g, int q, int nvec);      // (q: one top row, or -1: all rows)
+struct SkiRoute {
+    bool rowpoly = false;       // F M F^T (rl_rowpoly.h); otherwise W^T, grid product, W:
+    bool w_poly = false;        // the grid product may leave its expansion to k_spmv_w_poly
+    bool wt_staged = false, w_staged = false;   // k_spmv_wt_staged / k_spmv_w_staged (else CSR)
+    bool w_staged_p = false;    // k_spmv_w_staged_p may carry MINRES's P
+    bool grid_poly = false;     // the grid operator is wholly in the (verified) polynomial form
+    int rank = 0;               // rowpoly: basis size, partial sums per run, mixed coefficients
+    size_t rp_part_per_run = 0, lr_zhat = 0;
+};
+SkiRoute ski_route(const rl_ski* s, int nvec);
+bool ski_ready(const rl_ski* s, const SkiRoute& r);
+// What the caller of ONE K~ product asks for beyond it (default: nothing).  The solver's rounds
+// ride inside the product's kernels (rl_rowpoly.h): B in the projection (fuse), P in the expansion
+// or the staged W product (pfuse), its scalar head launched from `head` just before that kernel.
+struct Minres2Bufs;
+struct SkiCall {
+    RpFuse fuse{nullptr, nullptr, nullptr};
+    RpPFuse pfuse{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const Minres2Bufs* head = nullptr;     // (stays where the solver keeps it) ...
+    int head_par = 0;                      // ... and the round's parity
+    int* bump = nullptr;                   // the solver's round counter (first kernel bumps it)
+    bool noise = true;                     // false: W K_UU W^T x only, the caller adds eps (.) x
+};
+
+// ---------------------------------------------------------------------------
 // functions one translation unit defines and another calls
 // ---------------------------------------------------------------------------
 // rl_gridop.hip
@@ -579,6 +607,9 @@ int lr_ensure(rl_gridop* g);
 int lr_prepare(rl_gridop* g, int nvec);
 int lr_reserve(rl_gridop* g, int nvec);
 int gridop_prepare(rl_gridop* g, int nvec);
+// (rl_gridop_mvm + the W kernel's offer to expand lr_zhat itself; *expansion_deferred: taken)
+int gridop_mvm_int(rl_gridop* g, const double* X, double* Y, int nvec, hipStream_t stream,
+                   bool allow_deferred_expand, bool* expansion_deferred);
 int lr_all_coeffs(rl_gridop* g, int R, std::vector<double>* hC, std::vector<char>* exact,
                   std::vector<double>* captured);
 // (one chunk of a batched product on the transform kernels, optionally gathering W^T x itself:
@@ -590,13 +621,12 @@ int mvm_chunk_v1(rl_gridop* g, const MixParams& mp, const double* Xc, double* Yc
                  hipStream_t stream, const Gather* gather = nullptr, int* bump = nullptr);
 // rl_ski.hip
 int ski_reserve(rl_ski* s, int nvec);
-int ski_wt_int(rl_ski* s, const double* Xp, double* G, int nvec, hipStream_t st, int* bump = nullptr);
+int ski_wt_int(rl_ski* s, const SkiRoute& route, const double* Xp, double* G, int nvec, hipStream_t st,
+               int* bump = nullptr);
 int ski_reserve_perm(rl_ski* s, int nvec);
 void permute_rows(rl_ski* s, const double* X, double* Y, int nvec, int scatter, hipStream_t st);
-bool w_staged_p_ok(const rl_ski* s, int nvec);
-bool rp_ok(const rl_ski* s, int nvec);
 int rp_prepare(rl_ski* s, int nvec);
-bool rp_ready(const rl_ski* s, int nvec);
 int ski_mvm_int(rl_ski* s, const double* Xp, double* Yp, int nvec, hipStream_t st,
-                int* bump = nullptr, bool noise = true);
-
+                const SkiCall& call = SkiCall());
+// rl_solve.hip (the one call UP from rl_ski.hip into the solver's unit: SkiCall::head, k_minres2_ph)
+void minres2_head(const Minres2Bufs& mb, int par, hipStream_t st);

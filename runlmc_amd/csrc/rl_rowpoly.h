@@ -14,10 +14,10 @@
 //                                    staged through LDS)
 //     k_lr_mix       Zhat = nu (.) sum_q B_q C_q (nu (.) Z)          (rl_lowrank.h)
 //     k_rp_expand    Q = F Zhat (+ eps (.) Y)                         (scalar-loaded coefficients)
-// i.e. one read of Y, one write of Q and one read of F (the expansion computes its rows of F
-// from the interpolation entries, FLY below), against W^T (read Y, write g), projection
-// (read g), mix, W with expansion (write Q) before: 1.18 -> 0.60 ms per C5 round, DESIGN.md
-// section 6.
+// i.e. one read of Y, one write of Q and one read of F (the projection reads the table, the
+// expansion computes its rows of F from the interpolation entries: FLY below), against W^T
+// (read Y, write g), projection (read g), mix, W with expansion (write Q) before: 1.18 ->
+// 0.60 ms per C5 round, DESIGN.md section 6.
 // Same operator, another summation order (roundoff-level agreement, as k_spmv_w_poly).
 // Rows are in the handle's SORTED order (by output, then by grid position), so the rows of
 // an output are contiguous; F is degree-major, F[j * n + i].
@@ -76,8 +76,8 @@ k_rp_build(const int* __restrict__ base, const double* __restrict__ w4, int n, i
 }
 
 // A row's values of F straight from its interpolation entry (base column, four weights):
-// f(j) called for j = 0 .. R - 1 in order.  (FLY variants of the kernels below: no table --
-// F costs a 17-vector batch as much HBM traffic as its vectors do.)
+// f(j) called for j = 0 .. R - 1 in order.  (k_rp_expand<.., FLY = true>: no table -- F costs
+// a 17-vector batch as much HBM traffic as its vectors do.)
 struct RpRow {
     double w[4], s[4], qm[4], q[4];
     __device__ __forceinline__ void start(int b, int m, const double* __restrict__ w4row) {
@@ -207,12 +207,11 @@ __device__ __forceinline__ void rp_wave_sum2(double& a, double& b) {
 #endif
 }
 
-template <int R, bool FLY, bool FB = false>
+template <int R, bool FB = false>
 __global__ void __launch_bounds__(256) RL_RP_PROJECT_ATTR
 k_rp_project(const double* Y, int n, int nvec, const double* __restrict__ F,
              const int* __restrict__ runs, int nruns, double* __restrict__ part,
-             int* __restrict__ bump, const int* __restrict__ base, const double* __restrict__ w4,
-             int m, const double* __restrict__ beta, RpFuse fz = RpFuse{nullptr, nullptr, nullptr}) {
+             int* __restrict__ bump, RpFuse fz = RpFuse{nullptr, nullptr, nullptr}) {
     static_assert(R <= RL_RP_RMAX, "rank");
     double* Yw = const_cast<double*>(Y);     // (FB only: y_r stored over y')
     // (the solver's round counter: bumped by the first kernel of a round)
@@ -299,55 +298,33 @@ k_rp_project(const double* Y, int n, int nvec, const double* __restrict__ F,
         // (All loads first, unconditional from clamped positions, masked afterwards: a
         // conditional load is a branch with a full memory wait behind it -- the first version
         // paid a round trip per value: 457 us per C5 round)
-        if (FLY) {
-            // the tile's F values computed from the rows' interpolation entries: waves 0-1 run
-            // a row each (four recurrences), waves 2-3 clear the padding degrees
-            if (tid < TILE) {
-                int row = t0 + tid;
-                const bool live = row < r1;
-                row = live ? row : r1 - 1;
-                RpRow rw;
-                rw.start(base[row], m, w4 + (size_t)4 * row);
-#pragma unroll 4
-                for (int j = 0; j < R; ++j) {
-                    const double f = rw.next(beta[j]);
-                    Fs[j * LD + tid] = live ? f : 0.0;
-                }
-            } else {
-                for (int idx = R * TILE + tid - TILE; idx < 16 * NT * TILE; idx += 256 - TILE) {
-                    const int deg = idx / TILE, rr = idx - deg * TILE;
-                    Fs[deg * LD + rr] = 0.0;
+        constexpr int NF = R * TILE / 256;         // R even: exact
+        static_assert((R * TILE) % 256 == 0, "tile of F divides over the threads");
+        constexpr int NB = NF <= 12 ? NF : (NF + 1) / 2;      // values per batch (registers)
+#pragma unroll
+        for (int u0 = 0; u0 < NF; u0 += NB) {
+            double fr[NB];
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                const int uu = u0 + u < NF ? u0 + u : NF - 1;
+                const int idx = tid + 256 * uu, deg = idx / TILE, rr = idx - deg * TILE;
+                int row = t0 + rr;
+                row = row < r1 ? row : r1 - 1;
+                fr[u] = F[(size_t)deg * n + row];
+            }
+#pragma unroll
+            for (int u = 0; u < NB; ++u) {
+                if (u0 + u < NF) {
+                    const int idx = tid + 256 * (u0 + u), deg = idx / TILE, rr = idx - deg * TILE;
+                    Fs[deg * LD + rr] = t0 + rr < r1 ? fr[u] : 0.0;
                 }
             }
-        } else {
-            constexpr int NF = R * TILE / 256;         // R even: exact
-            static_assert((R * TILE) % 256 == 0, "tile of F divides over the threads");
-            constexpr int NB = NF <= 12 ? NF : (NF + 1) / 2;      // values per batch (registers)
-#pragma unroll
-            for (int u0 = 0; u0 < NF; u0 += NB) {
-                double fr[NB];
-#pragma unroll
-                for (int u = 0; u < NB; ++u) {
-                    const int uu = u0 + u < NF ? u0 + u : NF - 1;
-                    const int idx = tid + 256 * uu, deg = idx / TILE, rr = idx - deg * TILE;
-                    int row = t0 + rr;
-                    row = row < r1 ? row : r1 - 1;
-                    fr[u] = F[(size_t)deg * n + row];
-                }
-#pragma unroll
-                for (int u = 0; u < NB; ++u) {
-                    if (u0 + u < NF) {
-                        const int idx = tid + 256 * (u0 + u), deg = idx / TILE, rr = idx - deg * TILE;
-                        Fs[deg * LD + rr] = t0 + rr < r1 ? fr[u] : 0.0;
-                    }
-                }
-            }
-            // degrees R .. 16 NT - 1 of the last degree tile: zero (written once would do; the
-            // tile is small)
-            for (int idx = R * TILE + tid; idx < 16 * NT * TILE; idx += 256) {
-                const int deg = idx / TILE, rr = idx - deg * TILE;
-                Fs[deg * LD + rr] = 0.0;
-            }
+        }
+        // degrees R .. 16 NT - 1 of the last degree tile: zero (written once would do; the
+        // tile is small)
+        for (int idx = R * TILE + tid; idx < 16 * NT * TILE; idx += 256) {
+            const int deg = idx / TILE, rr = idx - deg * TILE;
+            Fs[deg * LD + rr] = 0.0;
         }
         if (lone && tid < TILE) {
             const bool live = t0 + tid < r1;
@@ -500,7 +477,7 @@ k_rp_project(const double* Y, int n, int nvec, const double* __restrict__ F,
 // here the NEXT tile's loads are in flight while the current tile is multiplied, and the
 // smaller footprint (one Y tile, 8 accumulator registers) admits three workgroups per CU.
 // C5, 17 vectors: 72 us against the general kernel's 84 (same box); with F computed from the
-// interpolation entries (FLY) 74 -- the table stays.
+// interpolation entries it measured 74 -- the table stays.
 //   grid (nruns)   block 256   LDS: F tile [16 NT][LD] + Y tile [16][LD] + lone [TILE]
 // ---------------------------------------------------------------------------
 #if !defined(RL_EMU)
@@ -509,12 +486,11 @@ k_rp_project(const double* Y, int n, int nvec, const double* __restrict__ F,
 #else
 #define RL_RP_PROJECT1_ATTR(R, FB)
 #endif
-template <int R, bool FLY, bool FB = false>
+template <int R, bool FB = false>
 __global__ void __launch_bounds__(256) RL_RP_PROJECT1_ATTR(R, FB)
 k_rp_project1(const double* Y, int n, int nvec, const double* __restrict__ F,
               const int* __restrict__ runs, double* __restrict__ part, int* __restrict__ bump,
-              const int* __restrict__ base, const double* __restrict__ w4, int m,
-              const double* __restrict__ beta, RpFuse fz = RpFuse{nullptr, nullptr, nullptr}) {
+              RpFuse fz = RpFuse{nullptr, nullptr, nullptr}) {
     static_assert(R <= RL_RP_RMAX, "rank");
     double* Yw = const_cast<double*>(Y);     // (FB: y_r stored over y', as in k_rp_project)
     const int nruns = gridDim.x;
@@ -557,23 +533,14 @@ k_rp_project1(const double* Y, int n, int nvec, const double* __restrict__ F,
         const int deg = idx / TILE, rr = idx - deg * TILE;
         Fs[deg * LD + rr] = 0.0;
     }
-    double fr[FLY ? 4 : NF], yr[NU], yr2[FB ? NU : 1], ytr = 0.0, ytr2 = 0.0;
-    int fb = 0;
+    double fr[NF], yr[NU], yr2[FB ? NU : 1], ytr = 0.0, ytr2 = 0.0;
     auto load_tile = [&](int t0) {
-        if (FLY) {
-            // (the row's interpolation entry instead of its R values of F)
-            const int row = t0 + (tid & (TILE - 1)) < r1 ? t0 + (tid & (TILE - 1)) : r1 - 1;
-            fb = base[row];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) fr[e] = w4[(size_t)4 * row + e];
-        } else {
-#pragma unroll
-            for (int u = 0; u < (FLY ? 4 : NF); ++u) {
-                const int idx = tid + 256 * u, deg = idx / TILE, rr = idx - deg * TILE;
-                int row = t0 + rr;
-                row = row < r1 ? row : r1 - 1;
-                fr[u] = F[(size_t)deg * n + row];
-            }
+        for (int u = 0; u < NF; ++u) {
+            const int idx = tid + 256 * u, deg = idx / TILE, rr = idx - deg * TILE;
+            int row = t0 + rr;
+            row = row < r1 ? row : r1 - 1;
+            fr[u] = F[(size_t)deg * n + row];
         }
         int yrow = t0 + (tid & (TILE - 1));
         yrow = yrow < r1 ? yrow : r1 - 1;
@@ -593,24 +560,10 @@ k_rp_project1(const double* Y, int n, int nvec, const double* __restrict__ F,
     load_tile(r0);
     const int nfull = lone ? nvec - 1 : nvec;           // vectors of the matrix-core block
     for (int t0 = r0; t0 < r1; t0 += TILE) {
-        if (FLY) {
-            // waves 0-1: a row each, four recurrences; degrees j = 0 .. R - 1 in order
-            if (tid < TILE) {
-                RpRow rw;
-                rw.start(fb, m, fr);
-                const bool live = t0 + tid < r1;
-#pragma unroll 4
-                for (int j = 0; j < R; ++j) {
-                    const double f = rw.next(beta[j]);
-                    Fs[j * LD + tid] = live ? f : 0.0;
-                }
-            }
-        } else {
 #pragma unroll
-            for (int u = 0; u < (FLY ? 4 : NF); ++u) {
-                const int idx = tid + 256 * u, deg = idx / TILE, rr = idx - deg * TILE;
-                Fs[deg * LD + rr] = t0 + rr < r1 ? fr[u] : 0.0;
-            }
+        for (int u = 0; u < NF; ++u) {
+            const int idx = tid + 256 * u, deg = idx / TILE, rr = idx - deg * TILE;
+            Fs[deg * LD + rr] = t0 + rr < r1 ? fr[u] : 0.0;
         }
 #pragma unroll
         for (int u = 0; u < NU; ++u) {

@@ -309,25 +309,22 @@ void permute_rows(rl_ski* s, const double* X, double* Y, int nvec, int scatter,
 // (measured at C5: DESIGN.md)
 static int staged_vgroups() { return 4; }
 
+// the 64 KiB dynamic-LDS opt-in of a staged kernel's three instantiations, once per device
+template <class K>
+static void staged_lds_optin(unsigned long long* seen, K k1, K k2, K k4) {
+    if (!first_on_device(seen)) return;
+    for (K k : {k1, k2, k4})
+        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+}
 // the three stages in INTERNAL row order
-int ski_wt_int(rl_ski* s, const double* Xp, double* G, int nvec, hipStream_t st, int* bump) {
-    // large batch, structured W^T whose workgroup ranges fit LDS: staged form
-    // (measured at C5, 129 vectors: see DESIGN.md)
+int ski_wt_int(rl_ski* s, const SkiRoute& route, const double* Xp, double* G, int nvec, hipStream_t st,
+               int* bump) {
     constexpr int VB = 8;
     const size_t lds = ((size_t)VB * s->terms[0].wt_xmax + s->terms[0].wt_emax) * sizeof(double);
-    if (s->terms[0].WT_lo != nullptr && s->terms[0].wt_xmax > 0 && lds <= 64 * 1024 &&
-        s->terms[0].wt_xmax <= 4 * RL_THREADS &&
-        ((size_t)s->ngrid * nvec >= ((size_t)1 << 22) || s->kn.staged_wt) && !s->kn.no_staged_wt) {
+    if (route.wt_staged) {
         trace_once("W^T product: k_spmv_wt_staged");
         static unsigned long long seen = 0;
-        if (first_on_device(&seen)) {
-            (void)hipFuncSetAttribute((const void*)k_spmv_wt_staged<VB, 1>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_spmv_wt_staged<VB, 2>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_spmv_wt_staged<VB, 4>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        }
+        staged_lds_optin(&seen, k_spmv_wt_staged<VB, 1>, k_spmv_wt_staged<VB, 2>, k_spmv_wt_staged<VB, 4>);
         const unsigned gx = (s->ngrid + RL_THREADS - 1) / RL_THREADS;
         const int vg = staged_vgroups();
         const dim3 grid(gx, ((nvec + VB - 1) / VB + vg - 1) / vg);
@@ -347,16 +344,8 @@ int ski_wt_int(rl_ski* s, const double* Xp, double* G, int nvec, hipStream_t st,
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
-// does the W product of a batch take the staged form?
-static bool w_staged_ok(const rl_ski* s, int nvec) {
-    constexpr int VB = 8;
-    const size_t lds = (size_t)VB * s->terms[0].w_xmax * sizeof(double);
-    return s->terms[0].W4_base != nullptr && s->terms[0].w_xmax > 0 && lds <= 64 * 1024 &&
-           s->terms[0].w_xmax <= 4 * RL_THREADS &&
-           ((size_t)s->n * nvec >= ((size_t)1 << 22) || s->kn.staged_wt) && !s->kn.no_staged_wt;
-}
 // ... and with MINRES's P inside (k_spmv_w_staged_p: the partial sums' words next to the tile,
-// row accesses by 32-bit byte offsets)?
+// row accesses by 32-bit byte offsets)
 static size_t w_staged_p_lds(const rl_ski* s) {
     constexpr int VB = 8;
     size_t lds = ((size_t)VB * s->terms[0].w_xmax + (size_t)staged_vgroups() * VB * 8) * sizeof(double);
@@ -365,32 +354,76 @@ static size_t w_staged_p_lds(const rl_ski* s) {
 #endif
     return lds;
 }
-bool w_staged_p_ok(const rl_ski* s, int nvec) {
-    return w_staged_ok(s, nvec) && w_staged_p_lds(s) <= 64 * 1024 && s->n < (1 << 28);
+// The route of a K~ product of nvec vectors (rl_host.h SkiRoute): the one place that knows.
+// (The interpolation kernels of the first term; further terms always run CSR products.)
+SkiRoute ski_route(const rl_ski* s, int nvec) {
+    constexpr int VB = 8;
+    const SkiTerm& t = s->terms[0];
+    const rl_gridop* g = s->g;
+    SkiRoute r;
+    // large batch (or the test hook), structured W / W^T whose workgroup ranges fit LDS: staged
+    // forms (measured at C5, 129 vectors: see DESIGN.md)
+    const bool staged_on = !s->kn.no_staged_wt;
+    const bool large_rows = (size_t)s->n * nvec >= ((size_t)1 << 22) || s->kn.staged_wt;
+    const size_t wt_lds = ((size_t)VB * t.wt_xmax + t.wt_emax) * sizeof(double);
+    r.wt_staged = t.WT_lo != nullptr && t.wt_xmax > 0 && wt_lds <= 64 * 1024 &&
+                  t.wt_xmax <= 4 * RL_THREADS &&
+                  ((size_t)s->ngrid * nvec >= ((size_t)1 << 22) || s->kn.staged_wt) && staged_on;
+    const bool w4 = t.W4_base != nullptr && t.w_xmax > 0;
+    r.w_staged = w4 && (size_t)VB * t.w_xmax * sizeof(double) <= 64 * 1024 &&
+                 t.w_xmax <= 4 * RL_THREADS && large_rows && staged_on;
+    r.w_staged_p = single_term(s) && r.w_staged && w_staged_p_lds(s) <= 64 * 1024 && s->n < (1 << 28);
+    r.grid_poly = g->lr_ok && !g->lr_dirty;
+    // the W product takes the grid values from the polynomial form's mixed coefficients
+    // (k_spmv_w_poly): staged W on a 1-D grid the polynomial form is eligible for; whether the
+    // operator IS in that form at a rank the kernel takes the grid handle decides when the
+    // product runs (its verification may still be pending here): GridRoute::deferrable
+    r.w_poly = w4 && t.w_xmax <= 2 * RL_THREADS &&
+               ((size_t)VB * t.w_xmax + (size_t)VB * 2 * RL_LR_RMAX) * sizeof(double) <= 64 * 1024 &&
+               large_rows && staged_on && (g->lr_try || g->lr_ok) && g->m >= 4 * RL_THREADS &&
+               s->ngrid == g->D * g->m && !s->kn.no_w_poly;
+    // the operator as F M F^T: single term, structured W on a 1-D grid, every top row in the
+    // polynomial form, a large system
+    r.rowpoly = single_term(s) && t.W4_base != nullptr && !t.h_base.empty() &&
+           !g->wide && !g->lead &&
+           g->lr_try && !g->lr_dirty && g->lr_ok && s->ngrid == g->D * g->m &&
+           s->n < (1 << 28) &&          // (k_rp_expand's row accesses carry 32-bit byte offsets)
+           // (the batch gate of the structured forms also gates this one: rl_gridop_set_form_gate
+           // with a huge value puts the whole operator back on the transform kernels)
+           (size_t)nvec * g->D * g->m >= g->lr_min && large_rows &&
+           // (F is read twice per product whatever the batch: at ranks above 32 a batch of a
+           // few dozen vectors is level with the interpolation products or behind them --
+           // C5, 17 vectors, rank 36: 0.615 against 0.587 ms per round; rank 24: 0.49 against 0.53)
+           // (... except batches of at most 17, which take the small-batch projection:
+           // rank 36, 17 vectors: see profiles/r04/rp_ab.txt)
+           (g->lr_r <= 32 || nvec >= 48 || nvec <= RL_RP_VG + 1 || s->kn.staged_wt) &&
+           staged_on && !s->kn.no_rp;
+    if (r.rowpoly) {
+        r.rank = g->lr_r;
+        r.rp_part_per_run = (size_t)nvec * r.rank;
+        r.lr_zhat = (size_t)nvec * g->D * RL_LR_RMAX;
+    }
+    return r;
 }
-static int ski_w_int(rl_ski* s, const double* G, double* Yp, int nvec, const double* diag,
-                     const double* X2p, hipStream_t st) {
+// F for the route's rank, the runs and the partial sums of the batch are there (rp_prepare)
+bool ski_ready(const rl_ski* s, const SkiRoute& r) {
+    return !r.rowpoly || (s->rp_F != nullptr && s->rp_R == r.rank && s->rp_runs != nullptr &&
+                          s->rp_part.cap >= (size_t)s->rp_nruns * r.rp_part_per_run &&
+                          s->g->lr_zhat.cap >= r.lr_zhat);
+}
+// (pf.pc != NULL: MINRES's P inside the product, no output vector -- ski_mvm_int checked that
+// the route admits it)
+static int ski_w_int(rl_ski* s, const SkiRoute& route, const double* G, double* Yp, int nvec,
+                     const double* diag, const double* X2p, hipStream_t st, const RpPFuse& pf) {
     // large batch, structured W: staged form (see ski_wt_int)
     constexpr int VB = 8;
     const size_t lds = (size_t)VB * s->terms[0].w_xmax * sizeof(double);
-    const RpPFuse pf = s->rp_pfuse;          // (by value: the solver clears the handle's copy)
+    const int vg = staged_vgroups();
+    const dim3 grid((s->n + RL_THREADS - 1) / RL_THREADS, ((nvec + VB - 1) / VB + vg - 1) / vg);
     if (pf.pc != nullptr) {
-        // MINRES's P inside the product (the solver checked w_staged_ok): no output vector
-        if (!w_staged_p_ok(s, nvec))
-            return fail(RL_EINVAL, "internal: MINRES update fused into a W product that does not run staged");
         trace_once("W product: k_spmv_w_staged_p (MINRES's P inside)");
         static unsigned long long seenp = 0;
-        if (first_on_device(&seenp)) {
-            (void)hipFuncSetAttribute((const void*)k_spmv_w_staged_p<VB, 1>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_spmv_w_staged_p<VB, 2>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_spmv_w_staged_p<VB, 4>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        }
-        const unsigned gx = (s->n + RL_THREADS - 1) / RL_THREADS;
-        const int vg = staged_vgroups();
-        const dim3 grid(gx, ((nvec + VB - 1) / VB + vg - 1) / vg);
+        staged_lds_optin(&seenp, k_spmv_w_staged_p<VB, 1>, k_spmv_w_staged_p<VB, 2>, k_spmv_w_staged_p<VB, 4>);
         const size_t ldsp = w_staged_p_lds(s);
 #define RL_W_STAGED_P(XPT)                                                                      \
     RL_LAUNCH((k_spmv_w_staged_p<VB, XPT>), grid, dim3(RL_THREADS), ldsp, st,                   \
@@ -403,20 +436,10 @@ static int ski_w_int(rl_ski* s, const double* G, double* Yp, int nvec, const dou
         RL_HIP(hipGetLastError());
         return RL_OK;
     }
-    if (w_staged_ok(s, nvec)) {
+    if (route.w_staged) {
         trace_once("W product: k_spmv_w_staged");
         static unsigned long long seen = 0;
-        if (first_on_device(&seen)) {
-            (void)hipFuncSetAttribute((const void*)k_spmv_w_staged<VB, 1>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_spmv_w_staged<VB, 2>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_spmv_w_staged<VB, 4>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        }
-        const unsigned gx = (s->n + RL_THREADS - 1) / RL_THREADS;
-        const int vg = staged_vgroups();
-        const dim3 grid(gx, ((nvec + VB - 1) / VB + vg - 1) / vg);
+        staged_lds_optin(&seen, k_spmv_w_staged<VB, 1>, k_spmv_w_staged<VB, 2>, k_spmv_w_staged<VB, 4>);
 #define RL_W_STAGED(XPT)                                                                        \
     RL_LAUNCH((k_spmv_w_staged<VB, XPT>), grid, dim3(RL_THREADS), lds, st,                      \
               (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, s->n, s->ngrid, \
@@ -432,20 +455,6 @@ static int ski_w_int(rl_ski* s, const double* G, double* Yp, int nvec, const dou
                 G, Yp, diag, X2p, st);
     RL_HIP(hipGetLastError());
     return RL_OK;
-}
-// can the W product of a batch take the grid values from the polynomial form's mixed
-// coefficients (k_spmv_w_poly)?  Staged W on a 1-D grid the polynomial form is eligible
-// for; whether the operator IS in that form at rank 24 or 32 the grid handle decides when
-// the product runs (its verification may still be pending here): lr_launch
-static bool ski_w_poly_ok(const rl_ski* s, int nvec) {
-    constexpr int VB = 8;
-    const rl_gridop* g = s->g;
-    const size_t lds = ((size_t)VB * s->terms[0].w_xmax + (size_t)VB * 2 * RL_LR_RMAX) * sizeof(double);
-    return s->terms[0].W4_base != nullptr && s->terms[0].w_xmax > 0 && s->terms[0].w_xmax <= 2 * RL_THREADS &&
-           lds <= 64 * 1024 && ((size_t)s->n * nvec >= ((size_t)1 << 22) || s->kn.staged_wt) &&
-           !s->kn.no_staged_wt &&
-           (g->lr_try || g->lr_ok) && g->m >= 4 * RL_THREADS && s->ngrid == g->D * g->m &&
-           !s->kn.no_w_poly;
 }
 static int ski_w_poly(rl_ski* s, double* Yp, int nvec, const double* diag, const double* X2p,
                       hipStream_t st) {
@@ -482,34 +491,11 @@ static int ski_w_poly(rl_ski* s, double* Yp, int nvec, const double* diag, const
 // ---------------------------------------------------------------------------
 // Row-polynomial form of large solver rounds (rl_rowpoly.h)
 // ---------------------------------------------------------------------------
-// may this handle's operator run as F M F^T for a batch of nvec vectors?  (single term,
-// structured W on a 1-D grid, every top row in the polynomial form, a large system)
-bool rp_ok(const rl_ski* s, int nvec) {
-    const rl_gridop* g = s->g;
-    return single_term(s) && s->terms[0].W4_base != nullptr && !s->terms[0].h_base.empty() &&
-           !g->wide && !g->lead &&
-           g->lr_try && !g->lr_dirty && g->lr_ok && s->ngrid == g->D * g->m &&
-           s->n < (1 << 28) &&          // (k_rp_expand's row accesses carry 32-bit byte offsets)
-           // (the batch gate of the structured forms also gates this one: rl_gridop_set_form_gate
-           // with a huge value puts the whole operator back on the transform kernels)
-           (size_t)nvec * g->D * g->m >= g->lr_min &&
-           ((size_t)s->n * nvec >= ((size_t)1 << 22) || s->kn.staged_wt) &&
-           // (F is read twice per product whatever the batch: at ranks above 32 a batch of a
-           // few dozen vectors is level with the interpolation products or behind them --
-           // C5, 17 vectors, rank 36: 0.615 against 0.587 ms per round; rank 24: 0.49 against 0.53)
-           // (... except batches of at most 17, which take the small-batch projection:
-           // rank 36, 17 vectors: see profiles/r04/rp_ab.txt)
-           (g->lr_r <= 32 || nvec >= 48 || nvec <= RL_RP_VG + 1 || s->kn.staged_wt) &&
-           !s->kn.no_staged_wt && !s->kn.no_rp;
-}
 // F for the operator's current rank, the runs of rows k_rp_project walks, the partial sums
 // of nvec vectors.  Allocates: never inside a stream capture (the solver calls it before).
 int rp_prepare(rl_ski* s, int nvec) {
     rl_gridop* g = s->g;
     const int R = g->lr_r, n = s->n, D = g->D, m = g->m;
-    if (s->rp_R != R && (s->kn.rp_fly & 2)) {
-        s->rp_R = R;                 // (no table: both kernels compute F from the entries)
-    }
     if (s->rp_R != R) {
         s->rp_R = 0;
         RL_TRY(s->rp_F.renew((size_t)R * n));
@@ -555,64 +541,53 @@ int rp_prepare(rl_ski* s, int nvec) {
     RL_TRY(lr_reserve(g, nvec));             // (the mixed coefficients live on the grid handle)
     return RL_OK;
 }
-bool rp_ready(const rl_ski* s, int nvec) {
-    return (s->rp_F != nullptr || (s->kn.rp_fly & 2)) && s->rp_R == s->g->lr_r && s->rp_runs != nullptr &&
-           s->rp_part.cap >= (size_t)s->rp_nruns * nvec * s->rp_R &&
-           s->g->lr_zhat.cap >= (size_t)nvec * s->g->D * RL_LR_RMAX;
-}
-template <int R, bool FLYP, bool FLYE>
+// (F: the table the projection reads; the expansion computes its rows of F from the
+// interpolation entries base / w4 -- all three in the row order of the batch)
+template <int R>
 static void rp_launch(rl_ski* s, const double* F, const int* base, const double* w4,
                       const double* Xp, double* Yp, int nvec, const double* diag, hipStream_t st,
-                      int* bump) {
+                      const SkiCall& call) {
     rl_gridop* g = s->g;
     constexpr int NT = (R + 15) / 16;
     const size_t lds = (((size_t)16 * NT + 2 * RL_RP_VG) * RL_RP_LD + RL_RP_TILE) * sizeof(double);
     const int vblk = RL_RP_NG(R) * RL_RP_VG;
-    const RpFuse fz = s->rp_fuse;            // (by value: the solver clears the handle's copy)
-    if constexpr (!FLYP) {
-        // at most one block of 16 vectors and a lone last one (a rank's share of an 8-way probe
-        // split): the small-batch kernel, next tile's loads in flight during the current one
-        if (nvec <= RL_RP_VG + 1 && (nvec <= RL_RP_VG || nvec % RL_RP_VG == 1) && !s->kn.no_rp_small) {
-            const size_t lds1 = (((size_t)16 * NT + RL_RP_VG) * RL_RP_LD + RL_RP_TILE) * sizeof(double);
-            // (F from the table: computed on the fly here it measured 74 against 72 us)
-            if (fz.r2 != nullptr)
-                RL_LAUNCH((k_rp_project1<R, false, true>), dim3(s->rp_nruns), dim3(256), lds1, st, Xp,
-                          s->n, nvec, F, (const int*)s->rp_runs, s->rp_part, bump, base, w4, g->m,
-                          (const double*)g->lr_beta, fz);
-            else
-                RL_LAUNCH((k_rp_project1<R, false>), dim3(s->rp_nruns), dim3(256), lds1, st, Xp, s->n,
-                          nvec, F, (const int*)s->rp_runs, s->rp_part, bump, base, w4, g->m,
-                          (const double*)g->lr_beta, RpFuse{nullptr, nullptr, nullptr});
-            goto projected;
-        }
-        if (fz.r2 != nullptr) {
-            const int vb = RL_RP_NG_FB(R) * RL_RP_VG;
-            RL_LAUNCH((k_rp_project<R, false, true>),
-                      dim3(8 * ((s->rp_nruns + 7) / 8) * ((nvec + vb - 1) / vb)), dim3(256), lds, st,
-                      Xp, s->n, nvec, F, (const int*)s->rp_runs, s->rp_nruns, s->rp_part, bump, base,
-                      w4, g->m, (const double*)g->lr_beta, fz);
-            goto projected;
-        }
+    const RpFuse& fz = call.fuse;
+    // at most one block of 16 vectors and a lone last one (a rank's share of an 8-way probe
+    // split): the small-batch kernel, next tile's loads in flight during the current one
+    if (nvec <= RL_RP_VG + 1 && (nvec <= RL_RP_VG || nvec % RL_RP_VG == 1) && !s->kn.no_rp_small) {
+        const size_t lds1 = (((size_t)16 * NT + RL_RP_VG) * RL_RP_LD + RL_RP_TILE) * sizeof(double);
+        if (fz.r2 != nullptr)
+            RL_LAUNCH((k_rp_project1<R, true>), dim3(s->rp_nruns), dim3(256), lds1, st, Xp,
+                      s->n, nvec, F, (const int*)s->rp_runs, s->rp_part, call.bump, fz);
+        else
+            RL_LAUNCH((k_rp_project1<R>), dim3(s->rp_nruns), dim3(256), lds1, st, Xp, s->n,
+                      nvec, F, (const int*)s->rp_runs, s->rp_part, call.bump,
+                      RpFuse{nullptr, nullptr, nullptr});
+    } else if (fz.r2 != nullptr) {
+        const int vb = RL_RP_NG_FB(R) * RL_RP_VG;
+        RL_LAUNCH((k_rp_project<R, true>),
+                  dim3(8 * ((s->rp_nruns + 7) / 8) * ((nvec + vb - 1) / vb)), dim3(256), lds, st,
+                  Xp, s->n, nvec, F, (const int*)s->rp_runs, s->rp_nruns, s->rp_part, call.bump, fz);
+    } else {
+        RL_LAUNCH((k_rp_project<R>), dim3(8 * ((s->rp_nruns + 7) / 8) * ((nvec + vblk - 1) / vblk)),
+                  dim3(256), lds, st, Xp, s->n, nvec, F, (const int*)s->rp_runs, s->rp_nruns, s->rp_part,
+                  call.bump, RpFuse{nullptr, nullptr, nullptr});
     }
-    RL_LAUNCH((k_rp_project<R, FLYP>), dim3(8 * ((s->rp_nruns + 7) / 8) * ((nvec + vblk - 1) / vblk)),
-              dim3(256), lds, st, Xp, s->n, nvec, F, (const int*)s->rp_runs, s->rp_nruns, s->rp_part,
-              bump, base, w4, g->m, (const double*)g->lr_beta, RpFuse{nullptr, nullptr, nullptr});
-projected:
     int split3 = 0;
     const size_t mix_lds = lr_mix_lds(g->D, R, g->Q, &split3);
     RL_LAUNCH(k_lr_mix, dim3(nvec), dim3(RL_LR_MIXT), mix_lds, st,
               (const double*)s->rp_part, 0, nvec, g->D, R, g->Q, (const double*)g->lr_C,
               (const double*)g->lr_B, (const double*)g->lr_nu, g->lr_zhat,
               (const int*)s->rp_run_ptr, split3);
-    if (s->rp_mid) s->rp_mid(st);
-    const RpPFuse pf = s->rp_pfuse;          // (by value: the solver clears the handle's copy)
+    if (call.head != nullptr) minres2_head(*call.head, call.head_par, st);
+    const RpPFuse& pf = call.pfuse;
     if (pf.pc != nullptr) {
         // MINRES's P inside the expansion: no operator output is written
-        size_t lds = (size_t)nvec * 8 * sizeof(double);
+        size_t ldsp = (size_t)nvec * 8 * sizeof(double);
 #if defined(RL_EMU)
-        lds += 256 * sizeof(double);
+        ldsp += 256 * sizeof(double);
 #endif
-        RL_LAUNCH((k_rp_expand<R, FLYE, true>), dim3((s->n + 255) / 256), dim3(256), lds, st,
+        RL_LAUNCH((k_rp_expand<R, true, true>), dim3((s->n + 255) / 256), dim3(256), ldsp, st,
                   (const double*)g->lr_zhat, F, s->n, nvec, g->D,
                   (const int*)s->rp_out_end, Yp, diag, Xp, s->kn.rp_stagger, base, w4, g->m,
                   (const double*)g->lr_beta, pf);
@@ -620,12 +595,12 @@ projected:
     }
     const RpPFuse nopf{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (diag != nullptr)
-        RL_LAUNCH((k_rp_expand<R, FLYE, false, true>), dim3((s->n + 255) / 256), dim3(256), 0, st,
+        RL_LAUNCH((k_rp_expand<R, true, false, true>), dim3((s->n + 255) / 256), dim3(256), 0, st,
                   (const double*)g->lr_zhat, F, s->n, nvec, g->D,
                   (const int*)s->rp_out_end, Yp, diag, Xp, s->kn.rp_stagger, base, w4, g->m,
                   (const double*)g->lr_beta, nopf);
     else
-        RL_LAUNCH((k_rp_expand<R, FLYE, false, false>), dim3((s->n + 255) / 256), dim3(256), 0, st,
+        RL_LAUNCH((k_rp_expand<R, true, false, false>), dim3((s->n + 255) / 256), dim3(256), 0, st,
                   (const double*)g->lr_zhat, F, s->n, nvec, g->D,
                   (const int*)s->rp_out_end, Yp, diag, Xp, s->kn.rp_stagger, base, w4, g->m,
                   (const double*)g->lr_beta, nopf);
@@ -652,66 +627,53 @@ static bool caller_order_same(rl_ski* s) {
 }
 // caller_order: the batch is in the caller's row order (F / entries permuted accordingly)
 static int ski_rp_mvm(rl_ski* s, bool caller_order, const double* Xp, double* Yp, int nvec,
-                      const double* diag, hipStream_t st, int* bump) {
+                      const double* diag, hipStream_t st, const SkiCall& call) {
     trace_once("K~ product: row-polynomial form (k_rp_project / k_lr_mix / k_rp_expand)");
-    const bool flyp = (s->kn.rp_fly & 2) != 0, flye = (s->kn.rp_fly & 1) != 0;
     const double* F = caller_order ? s->rp_Fc : s->rp_F;
     const int* base = caller_order ? s->rp_base_c : s->terms[0].W4_base;
     const double* w4 = caller_order ? s->rp_w4_c : s->terms[0].W4_w;
-#define RL_RP_CASE(R_)                                                                         \
-    case R_:                                                                                    \
-        if (flyp) rp_launch<R_, true, true>(s, F, base, w4, Xp, Yp, nvec, diag, st, bump);     \
-        else if (flye) rp_launch<R_, false, true>(s, F, base, w4, Xp, Yp, nvec, diag, st, bump); \
-        else rp_launch<R_, false, false>(s, F, base, w4, Xp, Yp, nvec, diag, st, bump);         \
-        break
     switch (s->g->lr_r) {
-        RL_RP_CASE(24); RL_RP_CASE(32); RL_RP_CASE(36); RL_RP_CASE(40); RL_RP_CASE(48);
+        case 24: rp_launch<24>(s, F, base, w4, Xp, Yp, nvec, diag, st, call); break;
+        case 32: rp_launch<32>(s, F, base, w4, Xp, Yp, nvec, diag, st, call); break;
+        case 36: rp_launch<36>(s, F, base, w4, Xp, Yp, nvec, diag, st, call); break;
+        case 40: rp_launch<40>(s, F, base, w4, Xp, Yp, nvec, diag, st, call); break;
+        case 48: rp_launch<48>(s, F, base, w4, Xp, Yp, nvec, diag, st, call); break;
         default: return fail(RL_EINVAL, "row-polynomial form: bad basis size");
     }
-#undef RL_RP_CASE
     RL_HIP(hipGetLastError());
     return RL_OK;
 }
-// Yp = K~ Xp, both in internal row order (what the solver iterates on)
-// (noise = false: Yp = W K_UU W^T Xp only -- the caller adds eps (.) Xp itself)
-int ski_mvm_int(rl_ski* s, const double* Xp, double* Yp, int nvec, hipStream_t st, int* bump,
-                bool noise) {
+// Yp = K~ Xp, both in internal row order (what the solver iterates on); `call`: what a solver
+// round asks beyond the product.  The SKI level's entry: it alone asks whether st is being captured.
+int ski_mvm_int(rl_ski* s, const double* Xp, double* Yp, int nvec, hipStream_t st, const SkiCall& call) {
     RL_TRY(ski_reserve(s, nvec));
-    const double* diag = s->has_noise && noise ? s->noise_diag.get() : nullptr;
+    const double* diag = s->has_noise && call.noise ? s->noise_diag.get() : nullptr;
+    // (only a single-term operator on a plain grid has routes that allocate or verify)
+    const bool structured = single_term(s) && !s->g->wide && !s->g->lead;
+    const bool capturing = structured && stream_capturing(st);
     // (a pending form decision is taken here, so that the path does not depend on whether an
     // earlier product happened to trigger it)
-    if (single_term(s) && !s->g->wide && !s->g->lead && !stream_capturing(st)) RL_TRY(lr_prepare(s->g, nvec));
-    // every top row in the polynomial form, a large system: F M F^T, no interpolation
-    // products, no grid vector (rl_rowpoly.h).  (Buffers: the solver prepares them before it
-    // captures; a plain product outside a capture prepares them here.)
-    if (rp_ok(s, nvec)) {
-        if (!rp_ready(s, nvec) && !stream_capturing(st)) RL_TRY(rp_prepare(s, nvec));
-        if (rp_ready(s, nvec)) {
-            return ski_rp_mvm(s, false, Xp, Yp, nvec, diag, st, bump);
-        }
-    }
-    // (the solver asked for its vector update inside the projection: no other path does it)
-    if (s->rp_fuse.r2 != nullptr)
-        return fail(RL_EINVAL, "internal: MINRES update fused into a projection that does not run");
-    // (the solver asked for P inside the W product: the staged kernel, a single term, and the
-    // grid vector written -- not the W kernel that expands the polynomial form itself)
-    const bool wp = s->rp_pfuse.pc != nullptr;
-    if (wp && (!single_term(s) || !w_staged_p_ok(s, nvec)))
-        return fail(RL_EINVAL, "internal: MINRES update fused into a W product that does not run staged");
-    RL_TRY(ski_wt_int(s, Xp, s->G1, nvec, st, bump));
-    // a polynomial-form operator hands its mixed coefficients to the W kernel instead of
-    // writing the grid vector (the grid handle says whether it took that path)
-    s->g->expand_deferred = false;
-    s->g->defer_expand = !wp && ski_w_poly_ok(s, nvec);
-    const int rc = rl_gridop_mvm(s->g, s->G1, s->G2, nvec, st);
-    s->g->defer_expand = false;
-    if (rc != RL_OK) return rc;
-    if (s->g->expand_deferred) {
-        s->g->expand_deferred = false;
+    if (structured && !capturing) RL_TRY(lr_prepare(s->g, nvec));
+    const SkiRoute route = ski_route(s, nvec);
+    // F M F^T, no interpolation products, no grid vector (rl_rowpoly.h): its buffers are prepared
+    // here outside a capture; a captured product that finds them short takes the other route
+    if (route.rowpoly && !ski_ready(s, route) && !capturing) RL_TRY(rp_prepare(s, nvec));
+    const bool rowpoly = route.rowpoly && ski_ready(s, route);
+    // the call's request against the route: B rides in the projection, P in the expansion or the staged W
+    const bool want_b = call.fuse.r2 != nullptr, want_p = call.pfuse.pc != nullptr;
+    if ((want_b && !rowpoly) || (want_p && !rowpoly && !route.w_staged_p))
+        return fail(RL_EINVAL, "internal: MINRES update fused into a product whose route does not run it");
+    if (rowpoly) return ski_rp_mvm(s, false, Xp, Yp, nvec, diag, st, call);
+    RL_TRY(ski_wt_int(s, route, Xp, s->G1, nvec, st, call.bump));
+    // a polynomial-form operator hands its mixed coefficients to the W kernel instead of writing the
+    // grid vector (the grid handle says whether it did) -- not when P rides in W, which reads it
+    bool expansion_deferred = false;
+    RL_TRY(gridop_mvm_int(s->g, s->G1, s->G2, nvec, st, route.w_poly && !want_p, &expansion_deferred));
+    if (expansion_deferred) {
         RL_TRY(ski_w_poly(s, Yp, nvec, diag, Xp, st));
     } else {
-        if (wp && s->rp_mid) s->rp_mid(st);       // (P's scalar head: k_minres2_ph)
-        RL_TRY(ski_w_int(s, s->G2, Yp, nvec, diag, Xp, st));
+        if (want_p && call.head != nullptr) minres2_head(*call.head, call.head_par, st);
+        RL_TRY(ski_w_int(s, route, s->G2, Yp, nvec, diag, Xp, st, call.pfuse));
     }
     for (size_t k = 1; k < s->terms.size(); ++k) {       // Yp += W_t K_t W_t^T Xp
         const SkiTerm& t = s->terms[k];
@@ -795,9 +757,9 @@ extern "C" int rl_ski_mvm(rl_ski* s, const double* X, double* Y, int nvec, void*
     // (constant per output) serve both.
     if (single_term(s) && !s->g->wide && !s->g->lead && !stream_capturing(st) && caller_order_same(s)) {
         RL_TRY(lr_prepare(s->g, nvec));
-        if (rp_ok(s, nvec)) {
+        if (ski_route(s, nvec).rowpoly) {
             RL_TRY(rp_prepare(s, nvec));
-            if (s->kn.rp_fly && (!s->rp_base_c || !s->rp_w4_c)) {
+            if (!s->rp_base_c || !s->rp_w4_c) {
                 // (a failed second allocation must not leave the first behind as a sign that
                 // both exist)
                 RL_TRY(s->rp_base_c.reserve((size_t)s->n));
@@ -811,7 +773,7 @@ extern "C" int rl_ski_mvm(rl_ski* s, const double* X, double* Y, int nvec, void*
                 RL_HIP(hipGetLastError());
                 RL_HIP(hipDeviceSynchronize());
             }
-            if (!(s->kn.rp_fly & 2) && s->rp_Fc_R != s->rp_R) {
+            if (s->rp_Fc_R != s->rp_R) {
                 s->rp_Fc_R = 0;
                 RL_TRY(s->rp_Fc.renew((size_t)s->rp_R * s->n));
                 permute_rows(s, s->rp_F, s->rp_Fc, s->rp_R, 1, (hipStream_t) nullptr);
@@ -820,7 +782,7 @@ extern "C" int rl_ski_mvm(rl_ski* s, const double* X, double* Y, int nvec, void*
                 s->rp_Fc_R = s->rp_R;
             }
             return ski_rp_mvm(s, true, X, Y, nvec, s->has_noise ? s->noise_diag.get() : nullptr, st,
-                              nullptr);
+                              SkiCall());
         }
     }
     RL_TRY(ski_reserve_perm(s, nvec));

@@ -99,10 +99,6 @@ static int minres_iteration(rl_ski* s, const MinresBufs& mb, SolverWork& w, int 
     return RL_OK;
 }
 
-// one round of the two-kernel MINRES (rl_solver.h): operator product on the
-// unnormalised Lanczos vector, P, B; identical arguments every round
-static bool g_is_v2(const rl_gridop* g) { return g->v2; }
-
 // Polynomial rounds of a small MINRES solve (rl_solver.h): are they possible for
 // this handle and batch, and if so build (once) the row blocks -- at most 1024 rows,
 // each inside ONE output -- and make sure the form is verified at rank RL_LR_RS.
@@ -159,8 +155,15 @@ static int poly_round_prepare(rl_ski* s, int nrhs, int max_blk, bool* ok) {
     return RL_OK;
 }
 
-static int minres2_round(rl_ski* s, const Minres2Bufs& mb, int nrhs, int n, int nblk, int round,
-                         double rtol, int maxiter, hipStream_t st) {
+void minres2_head(const Minres2Bufs& mb, int par, hipStream_t st) {
+    RL_LAUNCH(k_minres2_ph, dim3(mb.fuse_p), dim3(RL_SOLVER_THREADS),
+              RL_SOLVER_THREADS * sizeof(double), st, mb, par);
+}
+
+// one round of the two-kernel MINRES (rl_solver.h): operator product on the
+// unnormalised Lanczos vector, P, B; identical arguments every round
+static int minres2_round(rl_ski* s, const SkiRoute& route, const Minres2Bufs& mb, int nrhs, int n,
+                         int nblk, int round, double rtol, int maxiter, hipStream_t st) {
     const int par = (round - 1) & 1;
     dim3 grid(nblk, nrhs), blk(RL_SOLVER_THREADS);
     const size_t red = RL_SOLVER_THREADS * sizeof(double);
@@ -176,7 +179,7 @@ static int minres2_round(rl_ski* s, const Minres2Bufs& mb, int nrhs, int n, int 
         return RL_OK;
     }
     if (mb.W_indptr != nullptr && mb.fuse_wt) {
-        trace_once(g_is_v2(s->g) ? "minres round: W^T in k2_cols_fwd, W in P"
+        trace_once(s->g->v2 ? "minres round: W^T in k2_cols_fwd, W in P"
                                  : "minres round: W^T in k_cols_fwd, W in P");
         // W^T fused into the column transforms (gathered while loading), W into
         // P: three grid kernels, P, B
@@ -200,27 +203,25 @@ static int minres2_round(rl_ski* s, const Minres2Bufs& mb, int nrhs, int n, int 
                                 mb.giter));
     } else if (mb.W_indptr != nullptr) {
         // W product fused into P: only W^T and the grid product run here
-        RL_TRY(ski_wt_int(s, yin, s->G1, nrhs, st, mb.giter));
+        RL_TRY(ski_wt_int(s, route, yin, s->G1, nrhs, st, mb.giter));
         RL_TRY(rl_gridop_mvm(s->g, s->G1, s->G2, nrhs, st));
     } else {
+        // the operator as one product, carrying what minres2_plan chose (rl_host.h SkiCall):
         // row-polynomial operator: the previous round's B finishes inside this projection
         // (y_{r-1} = y' - coef y_{r-2} formed and stored while the tile is staged; rl_rowpoly.h)
-        if (mb.fuse_b && round >= 2) s->rp_fuse = RpFuse{mb.tri[par], mb.coef, mb.nrmB};
+        SkiCall call;
+        call.bump = mb.giter;
+        call.noise = mb.fuse_p || mb.eps_runs == 0;
+        if (mb.fuse_b && round >= 2) call.fuse = RpFuse{mb.tri[par], mb.coef, mb.nrmB};
         if (mb.fuse_p) {
-            // ... and this round's P inside the expansion (rl_rowpoly.h RpPFuse): its scalar
-            // head between the coefficient map and the expansion, no k_minres2_p
-            s->rp_pfuse = RpPFuse{mb.pc, mb.tri[par], mb.w[par], mb.w[1 - par], mb.x,
-                                  mb.partA[1 - par], mb.partC};
-            const Minres2Bufs mbc = mb;
-            s->rp_mid = [mbc, par](hipStream_t q) {
-                RL_LAUNCH(k_minres2_ph, dim3(mbc.fuse_p), dim3(RL_SOLVER_THREADS), red, q, mbc, par);
-            };
+            // ... and this round's P inside the expansion or the staged W product (rl_rowpoly.h
+            // RpPFuse): its scalar head just before that kernel, no k_minres2_p
+            call.pfuse = RpPFuse{mb.pc, mb.tri[par], mb.w[par], mb.w[1 - par], mb.x,
+                                 mb.partA[1 - par], mb.partC};
+            call.head = &mb;
+            call.head_par = par;
         }
-        const int rc = ski_mvm_int(s, yin, mb.q, nrhs, st, mb.giter, mb.fuse_p || mb.eps_runs == 0);
-        s->rp_fuse = RpFuse{nullptr, nullptr, nullptr};
-        s->rp_pfuse = RpPFuse{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        s->rp_mid = nullptr;
-        if (rc != RL_OK) return rc;
+        RL_TRY(ski_mvm_int(s, yin, mb.q, nrhs, st, call));
         if (mb.fuse_p) {
             RL_LAUNCH(k_minres2_bh, dim3(nrhs), blk, red, st, mb, mb.np, par, rtol, maxiter);
             // (P inside the W product: no projection carries B's vector work)
@@ -252,6 +253,130 @@ static int cg_iteration(rl_ski* s, SolverWork& w, double* X, int nrhs, int n, in
     RL_LAUNCH(k_cg_update, grid, blk, red, st, X, r, (const double*)p, (const double*)q, n,
               (const double*)w.S[0], w.I, (const double*)w.part[0], w.part[1]);
     RL_LAUNCH(k_count_iter, grid1, blk1, 0, st, w.I, nrhs);
+    return RL_OK;
+}
+
+// The plan of a two-kernel MINRES solve (rl_solver.h: Minres2Bufs): the buffer wiring and, from
+// the route of the batch's operator product, the three fusion choices -- B inside the row-polynomial
+// projection, P inside its expansion, P inside the staged W product.  (lanczos_cap > 0: recorded)
+static int minres2_plan(rl_ski* s, const SkiRoute& route, SolverWork& w, double* Xi, int nrhs, int n,
+                        int nblk, bool poly_round, int lanczos_cap, hipStream_t st, Minres2Bufs* plan) {
+    Minres2Bufs& mb = *plan = Minres2Bufs{};      // (every fusion off, nothing recorded)
+    mb.tri[0] = w.vec[0]; mb.tri[1] = w.vec[1];
+    mb.w[0] = w.vec[3]; mb.w[1] = w.vec[4];
+    mb.q = w.vec[6];
+    mb.x = Xi;
+    mb.S[0] = w.S[0]; mb.S[1] = w.S[1];
+    mb.I = w.I;
+    mb.giter = w.count + 1;
+    mb.partA[0] = w.part[0]; mb.partA[1] = w.part[3];
+    mb.partB = w.part[1];
+    mb.partC = w.part[2];
+    // the W product rides inside P when the problem is small enough to be
+    // launch-bound (a big one amortises the CSR over 8 vectors in k_spmv<8>)
+    const bool fuse_w = single_term(s) && (size_t)n * nrhs < ((size_t)1 << 22) &&
+                        !s->kn.no_fuse_w;
+    mb.W_indptr = fuse_w ? s->terms[0].W_indptr.get() : nullptr;
+    // ... and W^T inside the first grid kernel when that is a k2_cols_fwd and
+    // the batch is one chunk (the operator input is then the rotating buffer
+    // itself: no copy of the new Lanczos vector)
+    // (only while the rows of W^T are short -- about as many data points as grid
+    // points: a row of 30 entries, as on the weather workload, is a serial chain
+    // of gathers inside the transform kernel: 1.45 vs 1.23 s per fit)
+    const bool short_rows = (size_t)s->terms[0].nnzWT <= (size_t)8 * s->ngrid;
+    const bool fuse_wt = fuse_w && short_rows && s->g->Q >= 1 && !s->g->wide && !s->g->lead &&
+                         ((size_t)nrhs + 1) / 2 <= s->g->chunk_pairs &&
+                         !s->kn.no_fuse_wt;
+    mb.fuse_wt = fuse_wt ? 1 : 0;
+    mb.W_indices = s->terms[0].W_indices;
+    mb.W_data = s->terms[0].W_data;
+    mb.W_nnz = s->nnz;
+    mb.W4_base = s->terms[0].W4_base;
+    mb.W4_w = s->terms[0].W4_w;
+    mb.g = s->G2;
+    mb.eps = s->has_noise ? s->noise_diag.get() : nullptr;
+    mb.ngrid = s->ngrid;
+    mb.giter2 = w.count + 3;
+    if (poly_round && fuse_w) {
+        rl_gridop* g = s->g;
+        mb.poly_tab = s->poly_tab;
+        mb.poly_ob = s->poly_ob;
+        mb.poly_part = s->poly_part;
+        mb.poly_M = g->lr_M;
+        mb.poly_beta = g->lr_beta;
+        mb.poly_D = g->D;
+        mb.poly_m = g->m;
+    }
+    // single-term operator, W as its own kernel, noise in a few constant runs
+    // (one per output): the noise term moves into P
+    if (!fuse_w && single_term(s) && s->has_noise && !s->eps_end.empty()) {
+        mb.eps_runs = (int)s->eps_end.size();
+        for (int k = 0; k < mb.eps_runs; ++k) {
+            mb.eps_end[k] = s->eps_end[k];
+            mb.eps_val[k] = s->eps_val[k];
+        }
+    }
+    if (lanczos_cap > 0) {
+        const size_t bytes = (size_t)nrhs * lanczos_cap * 2 * sizeof(double);
+        RL_TRY(s->lanczos_buf.reserve(bytes / sizeof(double)));
+        w.lanczos = s->lanczos_buf;
+        RL_HIP(hipMemsetAsync(w.lanczos, 0, bytes, st));
+        mb.lanczos = w.lanczos;
+        mb.lanczos_cap = lanczos_cap;
+    }
+    // row-polynomial operator (every round of this solve takes it: the product's own route):
+    // B's vector work rides in the next round's projection
+    const bool rowpoly = route.rowpoly && ski_ready(s, route);
+    if (mb.W_indptr == nullptr && mb.poly_part == nullptr && rowpoly && !s->kn.no_rp_fuse) {
+        const size_t need = (size_t)nrhs * (s->rp_nruns + 1);
+        RL_TRY(s->rp_nrm.reserve(need));
+        mb.fuse_b = 1;
+        mb.coef = s->rp_nrm;
+        mb.nrmB = s->rp_nrm + nrhs;
+        mb.nrm_n = s->rp_nruns;
+        trace_once("minres round: B inside the row-polynomial projection (k_minres2_bh)");
+        // (the fused expansion keeps 8 doubles of LDS per system: past 1024 systems -- 64 KB --
+        // the launch would fail, so such batches keep P as its own kernel)
+        size_t pfuse_lds = (size_t)nrhs * 8 * sizeof(double);
+#if defined(RL_EMU)
+        pfuse_lds += 256 * sizeof(double);
+#endif
+        if (s->kn.rp_pfuse && pfuse_lds <= (size_t)64 * 1024) {
+            // ... and P inside the expansion (k_minres2_ph + k_rp_expand<.., true>)
+            const int np = (n + 255) / 256;
+            const size_t needp = (size_t)nrhs * (RL_RP_PCW + 3 * (size_t)np);
+            RL_TRY(s->rp_pp.reserve(needp));
+            RL_HIP(hipMemsetAsync(s->rp_pp, 0, needp * sizeof(double), st));
+            mb.fuse_p = nrhs;                 // (the head kernel's grid)
+            mb.pc = s->rp_pp;
+            mb.np = np;
+            mb.partA[0] = s->rp_pp + (size_t)nrhs * RL_RP_PCW;
+            mb.partA[1] = mb.partA[0] + (size_t)nrhs * np;
+            mb.partC = mb.partA[1] + (size_t)nrhs * np;
+            trace_once("minres round: P inside the row-polynomial expansion (k_minres2_ph)");
+        }
+    } else if (mb.W_indptr == nullptr && mb.poly_part == nullptr && s->kn.w_pfuse &&
+               route.w_staged_p &&
+               // (an operator wholly in the polynomial form has better rounds: row-polynomial
+               // ones, or the W kernel that expands the coefficients itself)
+               !route.grid_poly && !rowpoly) {
+        // interpolation products around a grid product (filter / transform forms): P inside
+        // the staged W product (k_minres2_ph + k_spmv_w_staged_p), B = k_minres2_bh + k_minres2_bv
+        const int np = (n + RL_THREADS - 1) / RL_THREADS;
+        const size_t needp = (size_t)nrhs * (RL_RP_PCW + 1 + 3 * (size_t)np);
+        RL_TRY(s->rp_pp.reserve(needp));
+        RL_HIP(hipMemsetAsync(s->rp_pp, 0, needp * sizeof(double), st));
+        mb.fuse_p = nrhs;
+        mb.pc = s->rp_pp;
+        mb.coef = s->rp_pp + (size_t)nrhs * RL_RP_PCW;
+        mb.np = np;
+        mb.partA[0] = mb.coef + nrhs;
+        mb.partA[1] = mb.partA[0] + (size_t)nrhs * np;
+        mb.partC = mb.partA[1] + (size_t)nrhs * np;
+        mb.nrmB = mb.partB;               // (k_minres2_bv's partial norms, one per solver block)
+        mb.nrm_n = nblk;
+        trace_once("minres round: P inside the staged W product (k_minres2_ph, k_spmv_w_staged_p)");
+    }
     return RL_OK;
 }
 
@@ -348,7 +473,9 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
     // everything the operator product allocates lazily must exist before capture
     RL_TRY(ski_reserve(s, nrhs));
     for (const SkiTerm& t : s->terms) RL_TRY(gridop_prepare(t.g, nrhs));
-    if (rp_ok(s, nrhs)) RL_TRY(rp_prepare(s, nrhs));       // (row-polynomial rounds: F, runs, partial sums)
+    // (the route every operator product of this solve takes: decided once the forms are verified)
+    const SkiRoute route = ski_route(s, nrhs);
+    if (route.rowpoly) RL_TRY(rp_prepare(s, nrhs));       // (row-polynomial rounds: F, runs, partial sums)
     int active = nrhs;
     int done = 0;          // iterations issued so far
 
@@ -364,132 +491,8 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
     if (method == RL_MINRES && !s->kn.minres_v1) {
         // two vector kernels per round (rl_solver.h: Minres2Bufs)
         Minres2Bufs mb;
-        mb.tri[0] = w.vec[0]; mb.tri[1] = w.vec[1];
-        mb.w[0] = w.vec[3]; mb.w[1] = w.vec[4];
-        mb.q = w.vec[6];
-        mb.x = Xi;
-        mb.S[0] = w.S[0]; mb.S[1] = w.S[1];
-        mb.I = w.I;
-        mb.giter = w.count + 1;
-        mb.partA[0] = w.part[0]; mb.partA[1] = w.part[3];
-        mb.partB = w.part[1];
-        mb.partC = w.part[2];
-        mb.lanczos = nullptr;
-        mb.lanczos_cap = 0;
-        // the W product rides inside P when the problem is small enough to be
-        // launch-bound (a big one amortises the CSR over 8 vectors in k_spmv<8>)
-        const bool fuse_w = single_term(s) && (size_t)n * nrhs < ((size_t)1 << 22) &&
-                            !s->kn.no_fuse_w;
-        mb.W_indptr = fuse_w ? s->terms[0].W_indptr.get() : nullptr;
-        // ... and W^T inside the first grid kernel when that is a k2_cols_fwd and
-        // the batch is one chunk (the operator input is then the rotating buffer
-        // itself: no copy of the new Lanczos vector)
-        // (only while the rows of W^T are short -- about as many data points as grid
-        // points: a row of 30 entries, as on the weather workload, is a serial chain
-        // of gathers inside the transform kernel: 1.45 vs 1.23 s per fit)
-        const bool short_rows = (size_t)s->terms[0].nnzWT <= (size_t)8 * s->ngrid;
-        const bool fuse_wt = fuse_w && short_rows && s->g->Q >= 1 && !s->g->wide && !s->g->lead &&
-                             ((size_t)nrhs + 1) / 2 <= s->g->chunk_pairs &&
-                             !s->kn.no_fuse_wt;
-        mb.fuse_wt = fuse_wt ? 1 : 0;
-        mb.W_indices = s->terms[0].W_indices;
-        mb.W_data = s->terms[0].W_data;
-        mb.W_nnz = s->nnz;
-        mb.W4_base = s->terms[0].W4_base;
-        mb.W4_w = s->terms[0].W4_w;
-        mb.g = s->G2;
-        mb.eps = s->has_noise ? s->noise_diag.get() : nullptr;
-        mb.ngrid = s->ngrid;
-        mb.poly_part = nullptr;
-        mb.giter2 = w.count + 3;
-        if (poly_round && fuse_w) {
-            rl_gridop* g = s->g;
-            mb.poly_tab = s->poly_tab;
-            mb.poly_ob = s->poly_ob;
-            mb.poly_part = s->poly_part;
-            mb.poly_M = g->lr_M;
-            mb.poly_beta = g->lr_beta;
-            mb.poly_D = g->D;
-            mb.poly_m = g->m;
-        }
-        // single-term operator, W as its own kernel, noise in a few constant runs
-        // (one per output): the noise term moves into P
-        mb.eps_runs = 0;
-        if (!fuse_w && single_term(s) && s->has_noise && !s->eps_end.empty()) {
-            mb.eps_runs = (int)s->eps_end.size();
-            for (int k = 0; k < mb.eps_runs; ++k) {
-                mb.eps_end[k] = s->eps_end[k];
-                mb.eps_val[k] = s->eps_val[k];
-            }
-        }
-        if (lanczos_out != nullptr) {
-            const size_t bytes = (size_t)nrhs * lanczos_cap * 2 * sizeof(double);
-            RL_TRY(s->lanczos_buf.reserve(bytes / sizeof(double)));
-            w.lanczos = s->lanczos_buf;
-            RL_HIP(hipMemsetAsync(w.lanczos, 0, bytes, st));
-            mb.lanczos = w.lanczos;
-            mb.lanczos_cap = lanczos_cap;
-        }
-        // row-polynomial operator (every round of this solve takes it: the same test as the
-        // product's): B's vector work rides in the next round's projection
-        mb.fuse_b = 0;
-        mb.coef = nullptr;
-        mb.nrmB = nullptr;
-        mb.nrm_n = 0;
-        mb.fuse_p = 0;
-        mb.pc = nullptr;
-        mb.np = 0;
-        if (mb.W_indptr == nullptr && mb.poly_part == nullptr && rp_ok(s, nrhs) && rp_ready(s, nrhs) &&
-            !(s->kn.rp_fly & 2) && !s->kn.no_rp_fuse) {
-            const size_t need = (size_t)nrhs * (s->rp_nruns + 1);
-            RL_TRY(s->rp_nrm.reserve(need));
-            mb.fuse_b = 1;
-            mb.coef = s->rp_nrm;
-            mb.nrmB = s->rp_nrm + nrhs;
-            mb.nrm_n = s->rp_nruns;
-            trace_once("minres round: B inside the row-polynomial projection (k_minres2_bh)");
-            // (the fused expansion keeps 8 doubles of LDS per system: past 1024 systems -- 64 KB --
-            // the launch would fail, so such batches keep P as its own kernel)
-            size_t pfuse_lds = (size_t)nrhs * 8 * sizeof(double);
-#if defined(RL_EMU)
-            pfuse_lds += 256 * sizeof(double);
-#endif
-            if (s->kn.rp_pfuse && pfuse_lds <= (size_t)64 * 1024) {
-                // ... and P inside the expansion (k_minres2_ph + k_rp_expand<.., true>)
-                const int np = (n + 255) / 256;
-                const size_t needp = (size_t)nrhs * (RL_RP_PCW + 3 * (size_t)np);
-                RL_TRY(s->rp_pp.reserve(needp));
-                RL_HIP(hipMemsetAsync(s->rp_pp, 0, needp * sizeof(double), st));
-                mb.fuse_p = nrhs;                 // (the head kernel's grid)
-                mb.pc = s->rp_pp;
-                mb.np = np;
-                mb.partA[0] = s->rp_pp + (size_t)nrhs * RL_RP_PCW;
-                mb.partA[1] = mb.partA[0] + (size_t)nrhs * np;
-                mb.partC = mb.partA[1] + (size_t)nrhs * np;
-                trace_once("minres round: P inside the row-polynomial expansion (k_minres2_ph)");
-            }
-        } else if (mb.W_indptr == nullptr && mb.poly_part == nullptr && s->kn.w_pfuse &&
-                   single_term(s) && w_staged_p_ok(s, nrhs) &&
-                   // (an operator wholly in the polynomial form has better rounds: row-polynomial
-                   // ones, or the W kernel that expands the coefficients itself)
-                   !(s->g->lr_ok && !s->g->lr_dirty) && !(rp_ok(s, nrhs) && rp_ready(s, nrhs))) {
-            // interpolation products around a grid product (filter / transform forms): P inside
-            // the staged W product (k_minres2_ph + k_spmv_w_staged_p), B = k_minres2_bh + k_minres2_bv
-            const int np = (n + RL_THREADS - 1) / RL_THREADS;
-            const size_t needp = (size_t)nrhs * (RL_RP_PCW + 1 + 3 * (size_t)np);
-            RL_TRY(s->rp_pp.reserve(needp));
-            RL_HIP(hipMemsetAsync(s->rp_pp, 0, needp * sizeof(double), st));
-            mb.fuse_p = nrhs;
-            mb.pc = s->rp_pp;
-            mb.coef = s->rp_pp + (size_t)nrhs * RL_RP_PCW;
-            mb.np = np;
-            mb.partA[0] = mb.coef + nrhs;
-            mb.partA[1] = mb.partA[0] + (size_t)nrhs * np;
-            mb.partC = mb.partA[1] + (size_t)nrhs * np;
-            mb.nrmB = mb.partB;               // (k_minres2_bv's partial norms, one per solver block)
-            mb.nrm_n = nblk;
-            trace_once("minres round: P inside the staged W product (k_minres2_ph, k_spmv_w_staged_p)");
-        }
+        RL_TRY(minres2_plan(s, route, w, Xi, nrhs, n, nblk, poly_round,
+                            lanczos_out != nullptr ? lanczos_cap : 0, st, &mb));
         RL_LAUNCH(k_minres2_init, grid, blk, 0, st, Bi, n, (const double*)w.part[0], mb);
         if (mb.poly_part != nullptr)        // projection of W^T y_0 for the first round's P
             RL_LAUNCH(k_poly_project_rows, grid, blk, 3 * RL_SOLVER_THREADS * sizeof(double), st,
@@ -499,7 +502,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
         // The first round runs eagerly so that graph replays of per_graph rounds
         // land on done = 1 + j * per_graph, i.e. on the reference's check points
         if (active > 0) {
-            RL_TRY(minres2_round(s, mb, nrhs, n, nblk, 1, rtol, maxiter, st));
+            RL_TRY(minres2_round(s, route, mb, nrhs, n, nblk, 1, rtol, maxiter, st));
             done = 1;
         }
         // graph replays start at round 2 + j * per2: the same parity every time
@@ -511,7 +514,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
             RL_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
             int rc = RL_OK;
             for (int k = 0; k < per2 && rc == RL_OK; ++k)
-                rc = minres2_round(s, mb, nrhs, n, nblk, 2 + k, rtol, maxiter, st);
+                rc = minres2_round(s, route, mb, nrhs, n, nblk, 2 + k, rtol, maxiter, st);
             hipError_t e = hipStreamEndCapture(st, &guard.graph);
             if (rc != RL_OK) return rc;
             RL_HIP(e);
@@ -548,7 +551,7 @@ static int solve_batch_impl(rl_ski* s, const double* B, double* X, int nrhs, int
                 RL_HIP(hipGraphLaunch(guard.exec, st));
                 done += per2;
             } else {
-                RL_TRY(minres2_round(s, mb, nrhs, n, nblk, done + 1, rtol, maxiter, st));
+                RL_TRY(minres2_round(s, route, mb, nrhs, n, nblk, done + 1, rtol, maxiter, st));
                 done += 1;
             }
             const bool check = check_every > 0 && (done - 1) % check_every == 0;
@@ -781,25 +784,21 @@ static void dz_tri_inverse(const std::vector<double>& L, int n, std::vector<doub
 template <int R>
 static void rp_project_plain(rl_ski* s, const double* Xp, int nvec, hipStream_t st,
                              const double* Ftab = nullptr, double* partbuf = nullptr) {
-    rl_gridop* g = s->g;
     const double* F_ = Ftab ? Ftab : (const double*)s->rp_F;
     double* part_ = partbuf ? partbuf : s->rp_part;
-    const double* beta_ = (const double*)g->lr_beta;       // (read by the table-free variants only)
     constexpr int NT = (R + 15) / 16;
     const RpFuse nofz{nullptr, nullptr, nullptr};
     if (nvec <= RL_RP_VG + 1 && (nvec <= RL_RP_VG || nvec % RL_RP_VG == 1) && !s->kn.no_rp_small) {
         const size_t lds1 = (((size_t)16 * NT + RL_RP_VG) * RL_RP_LD + RL_RP_TILE) * sizeof(double);
-        RL_LAUNCH((k_rp_project1<R, false>), dim3(s->rp_nruns), dim3(256), lds1, st, Xp, s->n, nvec,
-                  F_, (const int*)s->rp_runs, part_, (int*)nullptr,
-                  (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, g->m, beta_, nofz);
+        RL_LAUNCH((k_rp_project1<R>), dim3(s->rp_nruns), dim3(256), lds1, st, Xp, s->n, nvec,
+                  F_, (const int*)s->rp_runs, part_, (int*)nullptr, nofz);
         return;
     }
     const size_t lds = (((size_t)16 * NT + 2 * RL_RP_VG) * RL_RP_LD + RL_RP_TILE) * sizeof(double);
     const int vblk = RL_RP_NG(R) * RL_RP_VG;
-    RL_LAUNCH((k_rp_project<R, false>), dim3(8 * ((s->rp_nruns + 7) / 8) * ((nvec + vblk - 1) / vblk)),
+    RL_LAUNCH((k_rp_project<R>), dim3(8 * ((s->rp_nruns + 7) / 8) * ((nvec + vblk - 1) / vblk)),
               dim3(256), lds, st, Xp, s->n, nvec, F_, (const int*)s->rp_runs,
-              s->rp_nruns, part_, (int*)nullptr, (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w,
-              g->m, beta_, nofz);
+              s->rp_nruns, part_, (int*)nullptr, nofz);
 }
 // Yp = F zhat + diag (.) X2
 // (Ftab: expand from THAT table -- a block of the high-rank preconditioner's -- instead of the
@@ -816,16 +815,10 @@ static void rp_expand_plain(rl_ski* s, const double* zhat, double* Yp, int nvec,
                   (const double*)g->lr_beta, nopf);
         return;
     }
-    if (s->kn.rp_fly & 1)
-        RL_LAUNCH((k_rp_expand<R, true, false, true>), dim3((s->n + 255) / 256), dim3(256), 0, st, zhat,
-                  (const double*)s->rp_F, s->n, nvec, g->D, (const int*)s->rp_out_end, Yp, diag, X2,
-                  s->kn.rp_stagger, (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, g->m,
-                  (const double*)g->lr_beta, nopf);
-    else
-        RL_LAUNCH((k_rp_expand<R, false, false, true>), dim3((s->n + 255) / 256), dim3(256), 0, st, zhat,
-                  (const double*)s->rp_F, s->n, nvec, g->D, (const int*)s->rp_out_end, Yp, diag, X2,
-                  s->kn.rp_stagger, (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, g->m,
-                  (const double*)g->lr_beta, nopf);
+    RL_LAUNCH((k_rp_expand<R, true, false, true>), dim3((s->n + 255) / 256), dim3(256), 0, st, zhat,
+              (const double*)s->rp_F, s->n, nvec, g->D, (const int*)s->rp_out_end, Yp, diag, X2,
+              s->kn.rp_stagger, (const int*)s->terms[0].W4_base, (const double*)s->terms[0].W4_w, g->m,
+              (const double*)g->lr_beta, nopf);
 }
 #define RL_DZ_RANKS(CALL)                                                               \
     switch (s->g->lr_r) {                                                                \
@@ -1518,7 +1511,9 @@ static int pc_ensure(rl_ski* s, bool* ok, const char** why) {
     for (int j = 0; j < k; ++j) {
         RL_LAUNCH(k_pc_pick, dim3(1), dim3(256), red, st, (const double*)pc->pv, (const int*)pc->pi, nb, j, n,
                   pc->piv, pc->pivval, d0max, pc->e);
-        RL_TRY(ski_mvm_int(s, pc->e, pc->row, 1, st, nullptr, false));
+        SkiCall plain_no_noise;
+        plain_no_noise.noise = false;
+        RL_TRY(ski_mvm_int(s, pc->e, pc->row, 1, st, plain_no_noise));
         RL_LAUNCH(k_pc_step, dim3(nb), dim3(256), RL_PC_MAXRANK * sizeof(double) + red, st, j,
                   (const double*)pc->row, pc->L, n, (const int*)pc->piv, (const double*)pc->pivval,
                   (const double*)d0max, pc->rel_tol, pc->d, pc->mark, pc->pv, pc->pi);
@@ -1655,7 +1650,7 @@ static int dz_available(rl_ski* s, bool* ok, const char** why) {
     if (s->terms[0].W4_base == nullptr || s->terms[0].h_base.empty() || s->ngrid != g->D * g->m) {
         *why = "W is not a cubic interpolant of a 1-D grid"; return RL_OK;
     }
-    if (!g->lr_try || g->kn.no_rp || (s->kn.rp_fly & 2)) { *why = "polynomial form switched off or grid not eligible"; return RL_OK; }
+    if (!g->lr_try || g->kn.no_rp) { *why = "polynomial form switched off or grid not eligible"; return RL_OK; }
     if (s->n >= (1 << 28)) { *why = "n >= 2^28"; return RL_OK; }
     if (g->Q < 1) { *why = "no parameters set"; return RL_OK; }
     if (!s->has_noise || (int)s->h_noise.size() != s->n) { *why = "no noise set"; return RL_OK; }
@@ -1959,7 +1954,7 @@ extern "C" int rl_solve_direct(rl_ski* s, const double* B, double* X, int nrhs, 
     RL_TRY(rp_prepare(s, std::max(nrhs, R)));
     RL_TRY(ski_reserve(s, nrhs));
     RL_TRY(gridop_prepare(g, nrhs));
-    if (rp_ok(s, nrhs)) RL_TRY(rp_prepare(s, nrhs));
+    if (ski_route(s, nrhs).rowpoly) RL_TRY(rp_prepare(s, nrhs));
     RL_TRY(ski_reserve_perm(s, nrhs));
     const size_t ve = (size_t)nrhs * n;
     if (s->dz_vec_cap < ve) {
@@ -2120,7 +2115,7 @@ static int pcg_core(rl_ski* s, const double* B, double* X, int nrhs, double tol,
     if (!pcm) RL_TRY(rp_prepare(s, std::max(nrhs, R)));
     RL_TRY(ski_reserve(s, nrhs));
     for (size_t t = 0; t < (pcm ? s->terms.size() : 1); ++t) RL_TRY(gridop_prepare(s->terms[t].g, nrhs));
-    if (rp_ok(s, nrhs)) RL_TRY(rp_prepare(s, nrhs));
+    if (ski_route(s, nrhs).rowpoly) RL_TRY(rp_prepare(s, nrhs));
     RL_TRY(ski_reserve_perm(s, nrhs));
     if (pcm) RL_TRY(pc_reserve(s, nrhs));
     else if (s->dz_hz) RL_TRY(hz_reserve(s, nrhs));
