@@ -203,6 +203,17 @@ int rl_ski_add_term(rl_ski* s, rl_gridop* g, const int* W_indptr, const int* W_i
 /* noise host [D], lens host [D] (sum lens == n): eps repeated per output
  * (np.repeat(noise, lens), grid_kernel.py:70).                               */
 int rl_ski_set_noise(rl_ski* s, const double* noise, const int* lens);
+/* Known per-observation variances on top: e = np.repeat(noise, lens) + extra, extra host [n] >= 0
+ * in the CALLER's row order (the order of W's rows; the handle permutes it as it permutes the
+ * diagonal of rl_ski_set_noise).  K~ = sum_t W_t K_t W_t^T + diag(e); extra is never a parameter.
+ * The handle becomes a row-noise handle: its factorisation (rl_ski_factor, rl_solve_direct,
+ * rl_solve_pcg*, rl_ski_precond_*, rl_ski_inverse_diag) is that of the symmetrically scaled
+ * unit-noise problem K~ = E^1/2 (F~ M F~^T + I) E^1/2, F~ = diag(e^-1/2) F, whatever the rows'
+ * order; the 96-function preconditioner (mode 3) declines and the 48 functions (mode 2) take its
+ * place.  A later rl_ski_set_noise returns the handle to the per-output state.  RL_EINVAL: NULL,
+ * a negative or non-finite extra, sum(lens) != n.  (Joined ABI version 8 without a bump: no
+ * declared signature changed.)                                                                  */
+int rl_ski_set_noise_rows(rl_ski* s, const double* noise, const int* lens, const double* extra);
 /* Y[v] = K~ X[v];  X, Y dev [nvec][n]; may not alias.                        */
 int rl_ski_mvm(rl_ski* s, const double* X, double* Y, int nvec, void* stream);
 /* G[v] = W^T X[v] (dev [nvec][D*m])  /  Y[v] = W G[v] (dev [nvec][n]).      */
@@ -464,6 +475,14 @@ int rl_exact_set_separable(rl_exact* h, const double* X, const int* lens, int D,
                            const int* nfact, const int* leaf_kinds, const double* leaf_params,
                            const int* leaf_cols, const int* scaled, const double* scales,
                            const double* B, const double* noise);
+/* Known per-observation variances extra host [n] >= 0 (rows as in rl_exact_set*; NULL clears
+ * them), added to the diagonal wherever the per-output noise is: rl_exact_assemble and
+ * rl_exact_dense_host.  The noise-free cross-covariances (rl_exact_cross_*,
+ * rl_exact_explained_variance's right-hand sides) do not see them.  Kept on the handle across
+ * rl_exact_set* calls; a matrix assembled or factored before the call is dropped.  The noise
+ * slot of rl_exact_grad_sums stays the sum of M_ii per output.  RL_EINVAL: a negative or
+ * non-finite value.  (Joined ABI version 8 without a bump.)                                    */
+int rl_exact_set_row_noise(rl_exact* h, const double* extra);
 /* K into the device buffer (lower triangle; rl_exact_factor does it when needed). */
 int rl_exact_assemble(rl_exact* h);
 /* Blocked Cholesky K = L L^T in place (cho_factor, likelihood.py:153) and

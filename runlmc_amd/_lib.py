@@ -50,6 +50,7 @@ _SIGNATURES = {
     'rl_ski_apply_wt_term': [_vp, _i, _vp, _vp, _i, _vp],
     'rl_ski_apply_w_term': [_vp, _i, _vp, _vp, _i, _vp],
     'rl_ski_set_noise': [_vp, _vp, _vp],
+    'rl_ski_set_noise_rows': [_vp, _vp, _vp, _vp],
     'rl_ski_mvm': [_vp, _vp, _vp, _i, _vp],
     'rl_ski_apply_wt': [_vp, _vp, _vp, _i, _vp],
     'rl_ski_apply_w': [_vp, _vp, _vp, _i, _vp],
@@ -73,6 +74,7 @@ _SIGNATURES = {
     'rl_exact_set': [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
     'rl_exact_set_factors': [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'rl_exact_set_separable': [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'rl_exact_set_row_noise': [_vp, _vp],
     'rl_exact_assemble': [_vp],
     'rl_exact_factor': [_vp, _c_dbl_p, _c_int_p],
     'rl_exact_solve': [_vp, _vp, _vp, _i, _vp],

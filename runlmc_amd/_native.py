@@ -279,6 +279,20 @@ class SkiOp:
             raise ValueError('noise and lens must have one entry per output')
         self.lib.call('rl_ski_set_noise', self._h, host_ptr(noise), host_ptr(lens))
 
+    def set_noise_rows(self, noise, lens, extra):
+        """K~'s diagonal becomes repeat(noise, lens) + extra: known per-observation variances
+        `extra` (n values >= 0, the order of W's rows) on top of the per-output noise
+        (rl_ski_set_noise_rows).  A later set_noise returns to the per-output state."""
+        noise = as_f64(noise)
+        lens = np.ascontiguousarray(np.asarray(lens), dtype=np.int32)
+        if noise.shape != (self.grid.D,) or lens.shape != (self.grid.D,):
+            raise ValueError('noise and lens must have one entry per output')
+        extra = np.ascontiguousarray(as_f64(extra).reshape(-1))
+        if extra.shape != (self.n,):
+            raise ValueError('extra must have one entry per observation (%d), got %d'
+                             % (self.n, extra.size))
+        self.lib.call('rl_ski_set_noise_rows', self._h, host_ptr(noise), host_ptr(lens), host_ptr(extra))
+
     def factor(self):
         """(available, logdet, cond): builds / refreshes the Woodbury factorisation of
         K~ = F M F^T + diag(eps) for the current parameters (include/runlmc_hip.h:
@@ -839,6 +853,18 @@ class ExactOp:
             self.lib.call('rl_exact_set', self._h, host_ptr(X), host_ptr(lens), D, len(kinds),
                           host_ptr(kinds), host_ptr(params), host_ptr(cols), host_ptr(B), host_ptr(noise))
         self.D, self.Q, self.nder = D, len(kinds), nder
+
+    def set_row_noise(self, extra):
+        """Known per-observation variances (n values >= 0, rows as in `set`; None clears them) on
+        the diagonal next to the per-output noise: rl_exact_set_row_noise.  Kept across `set`."""
+        if extra is None:
+            self.lib.call('rl_exact_set_row_noise', self._h, None)
+            return
+        extra = np.ascontiguousarray(as_f64(extra).reshape(-1))
+        if extra.shape != (self.n,):
+            raise ValueError('extra must have one entry per observation (%d), got %d'
+                             % (self.n, extra.size))
+        self.lib.call('rl_exact_set_row_noise', self._h, host_ptr(extra))
 
     def assemble(self):
         self.lib.call('rl_exact_assemble', self._h)

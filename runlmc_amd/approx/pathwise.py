@@ -241,7 +241,10 @@ class PathwiseDraws:
 
     def __call__(self, Xs, noise=False):
         """One (size, len(Xs[d])) array per output, de-normalised; noise=True adds
-        observation noise (independent per draw and test point)."""
+        observation noise (independent per draw and test point): that of a NEW observation,
+        the per-output eps_d alone -- a model's fixed_noise belongs to its training rows (the
+        data side of Matheron's rule uses sqrt(eps_d + v_i) per training row, the operator's
+        diagonal)."""
         from .interpolation import multi_interpolant
         model = self._model
         if len(Xs) != model.output_dim:

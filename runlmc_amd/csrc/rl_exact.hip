@@ -3,6 +3,7 @@
 // K, then its Cholesky factor L, then (for gradients) the lower triangle of K^-1.
 #include "rl_host.h"
 #include "rl_exact.h"
+#include "rl_rownoise.h"
 
 enum { EX_EMPTY = 0, EX_SET, EX_ASSEMBLED, EX_FACTORED, EX_INVERTED };
 
@@ -21,6 +22,8 @@ struct rl_exact {
     DevBuf<int> dslot;
     DevBuf<double> Bm;              // Q x D x D
     DevBuf<double> noise;           // D
+    DevBuf<double> row_noise;       // n: known per-observation variances on top (rl_exact_set_row_noise) ...
+    bool has_row_noise = false;     // ... kept across rl_exact_set* calls until cleared
     DevBuf<double> logd;            // n
     DevBuf<double> scal;            // 1
     DevBuf<int> flag;               // first bad pivot
@@ -135,6 +138,12 @@ static int ex_cross(rl_exact* h, hipStream_t st, double* out, const double* Xa, 
               h->P, h->Q, (const int*)h->kinds, (const double*)h->prm, (const int*)h->cols,
               (const double*)h->Bm, h->D, noise, diag_off, 0);
     RL_HIP(hipGetLastError());
+    // (the per-observation variances go where the noise goes: not on the noise-free cross-covariances)
+    if (noise && h->has_row_noise) {
+        RL_LAUNCH(k_rn_add_diag, dim3((nrows + 255) / 256), dim3(256), 0, st, out, (long long)h->n, nrows,
+                  h->n, (const double*)h->row_noise, diag_off);
+        RL_HIP(hipGetLastError());
+    }
     return RL_OK;
 }
 
@@ -396,8 +405,32 @@ extern "C" int rl_exact_assemble(rl_exact* h) {
               (const int*)h->out_of, h->P, h->Q, (const int*)h->kinds, (const double*)h->prm,
               (const int*)h->cols, (const double*)h->Bm, h->D, (const double*)h->noise, 0, 1);
     RL_HIP(hipGetLastError());
+    if (h->has_row_noise) {
+        RL_LAUNCH(k_rn_add_diag, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)0, h->A.get(), (long long)n,
+                  n, n, (const double*)h->row_noise, 0);
+        RL_HIP(hipGetLastError());
+    }
     RL_HIP(hipStreamSynchronize(0));
     h->state = EX_ASSEMBLED;
+    return RL_OK;
+}
+
+// Known per-observation variances (host [n], the rows' order of rl_exact_set; NULL clears them):
+// added to the diagonal wherever the per-output noise is -- rl_exact_assemble, rl_exact_dense_host.
+// A matrix assembled or factored before the call is stale: the handle returns to its set state.
+extern "C" int rl_exact_set_row_noise(rl_exact* h, const double* extra) {
+    if (!h) return fail(RL_EINVAL, "rl_exact_set_row_noise: NULL handle");
+    if (extra) {
+        for (int i = 0; i < h->n; ++i)
+            if (!(extra[i] >= 0.0) || !std::isfinite(extra[i]))
+                return fail(RL_EINVAL, "rl_exact_set_row_noise: extra[" + std::to_string(i) +
+                                           "] is negative or not finite");
+        RL_HIP(hipSetDevice(h->device));
+        RL_TRY(h->row_noise.reserve((size_t)h->n));
+        RL_HIP(hipMemcpy(h->row_noise, extra, (size_t)h->n * sizeof(double), hipMemcpyHostToDevice));
+    }
+    h->has_row_noise = extra != nullptr;
+    if (h->state > EX_SET) h->state = EX_SET;
     return RL_OK;
 }
 

@@ -545,6 +545,19 @@ struct rl_ski {
     DevBuf<int> dz_go;               // dev [cap]: systems still being refined
     size_t dz_rhs_cap = 0;
     PcState pc;                         // the pivoted-Cholesky preconditioner (rl_ski_set_pivchol)
+    // per-observation noise (rl_rownoise.h): the factorisation of a handle whose noise came from
+    // rl_ski_set_noise_rows runs on the unit-noise problem of the scaled table F~ = diag(e^-1/2) F
+    bool row_noise = false;             // the noise is rl_ski_set_noise_rows' (rl_ski_set_noise clears it)
+    bool dz_rows = false;               // the valid factorisation (dz_Zt, dz_logdet) is of that scaled form
+    DevBuf<double> rn_isq, rn_sq, rn_inv, rn_one;   // dev [n]: e^-1/2, e^1/2, 1 / e, ones (internal row order)
+    double rn_sumlog = 0.0;             // sum_i log e_i, rows in internal order
+    const char* rn_why = nullptr;       // why those do not exist (a noise that is not positive)
+    unsigned long long rn_ver = ~0ull;  // noise_ver they were derived from
+    DevBuf<double> rn_F;                // dev [R][n]: F~, degree-major like rp_F (which stays unscaled)
+    int rn_F_R = 0;
+    unsigned long long rn_F_ver = ~0ull;
+    std::vector<double> rn_U;           // host [D][R][R]: F~_d^T F~_d, per noise update (dz_U stays F's)
+    DevBuf<double> rn_tmp;              // dev [cap][n]: the scaled input of an apply
 };
 
 inline bool single_term(const rl_ski* s) { return s->terms.size() == 1; }

@@ -230,16 +230,23 @@ extern "C" int rl_ski_destroy(rl_ski* s) {
     return RL_OK;
 }
 
-extern "C" int rl_ski_set_noise(rl_ski* s, const double* noise, const int* lens) {
-    if (!s || !noise || !lens) return fail(RL_EINVAL, "rl_ski_set_noise: NULL argument");
-    std::vector<double> diag;
-    diag.reserve(s->n);
+// the diagonal repeat(noise, lens) in the caller's row order, checked against the handle
+static int ski_noise_diag(const rl_ski* s, const char* who, const double* noise, const int* lens,
+                          std::vector<double>* diag) {
+    diag->clear();
+    diag->reserve(s->n);
     for (int d = 0; d < s->g->D; ++d) {
-        if (lens[d] < 0) return fail(RL_EINVAL, "rl_ski_set_noise: negative length");
-        diag.insert(diag.end(), (size_t)lens[d], noise[d]);
+        if (lens[d] < 0) return fail(RL_EINVAL, std::string(who) + ": negative length");
+        diag->insert(diag->end(), (size_t)lens[d], noise[d]);
     }
-    if ((int)diag.size() != s->n)
-        return fail(RL_EINVAL, "rl_ski_set_noise: sum(lens) != n");
+    if ((int)diag->size() != s->n)
+        return fail(RL_EINVAL, std::string(who) + ": sum(lens) != n");
+    return RL_OK;
+}
+
+// what rl_ski_set_noise and rl_ski_set_noise_rows share: a diagonal in the caller's row order
+// becomes the handle's (permuted, its runs, the device array, a new noise version)
+static int ski_install_noise(rl_ski* s, std::vector<double>& diag) {
     s->caller_noise_same = true;
     if (s->permuted) {
         std::vector<double> sorted(diag.size());
@@ -270,6 +277,33 @@ extern "C" int rl_ski_set_noise(rl_ski* s, const double* noise, const int* lens)
     s->has_noise = true;
     s->h_noise.swap(diag);
     ++s->noise_ver;
+    return RL_OK;
+}
+
+extern "C" int rl_ski_set_noise(rl_ski* s, const double* noise, const int* lens) {
+    if (!s || !noise || !lens) return fail(RL_EINVAL, "rl_ski_set_noise: NULL argument");
+    std::vector<double> diag;
+    RL_TRY(ski_noise_diag(s, "rl_ski_set_noise", noise, lens, &diag));
+    RL_TRY(ski_install_noise(s, diag));
+    s->row_noise = false;
+    return RL_OK;
+}
+
+// e = repeat(noise, lens) + extra, extra >= 0 per observation in the caller's row order (known
+// variances: never a parameter).  Marks the handle: its factorisation takes the scaled form of
+// rl_rownoise.h, where a diagonal set through rl_ski_set_noise must be constant per output.
+extern "C" int rl_ski_set_noise_rows(rl_ski* s, const double* noise, const int* lens, const double* extra) {
+    if (!s || !noise || !lens || !extra) return fail(RL_EINVAL, "rl_ski_set_noise_rows: NULL argument");
+    std::vector<double> diag;
+    RL_TRY(ski_noise_diag(s, "rl_ski_set_noise_rows", noise, lens, &diag));
+    for (int i = 0; i < s->n; ++i) {
+        if (!(extra[i] >= 0.0) || !std::isfinite(extra[i]))
+            return fail(RL_EINVAL, "rl_ski_set_noise_rows: extra[" + std::to_string(i) +
+                                       "] is negative or not finite");
+        diag[i] += extra[i];
+    }
+    RL_TRY(ski_install_noise(s, diag));
+    s->row_noise = true;
     return RL_OK;
 }
 

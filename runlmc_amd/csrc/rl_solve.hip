@@ -6,6 +6,7 @@
 #include "rl_direct.h"
 #include "rl_loo.h"
 #include "rl_pivchol.h"
+#include "rl_rownoise.h"
 #include <chrono>
 
 static size_t ws_cache_limit(const rl_ski* s) {
@@ -1663,6 +1664,90 @@ static int dz_available(rl_ski* s, bool* ok, const char** why) {
     return RL_OK;
 }
 
+// Per-observation noise (rl_rownoise.h): the row scalings and sum log e per NOISE update, the
+// scaled table F~ = diag(e^-1/2) F and its Gram matrices per (noise update, rank).  rp_F stays
+// unscaled (rl_ski_project and the gradient's coefficients need F^T x of the real F), dz_U stays
+// the cached Gram matrices of F.  *why is set when the noise admits no scaling.
+static int rn_ensure(rl_ski* s, int R, hipStream_t st, const char** why) {
+    const int n = s->n, D = s->g->D;
+    if (s->rn_ver != s->noise_ver) {
+        s->rn_why = nullptr;
+        std::vector<double> isq((size_t)n), sq((size_t)n), inv((size_t)n);
+        double sl = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const double e = s->h_noise[i];
+            if (!(e > 0.0) || !std::isfinite(e)) { s->rn_why = "noise is not positive"; break; }
+            sq[i] = std::sqrt(e);
+            isq[i] = 1.0 / sq[i];
+            inv[i] = 1.0 / e;
+            sl += std::log(e);
+        }
+        if (!s->rn_why) {
+            RL_TRY(s->rn_isq.reserve((size_t)n));
+            RL_TRY(s->rn_sq.reserve((size_t)n));
+            RL_TRY(s->rn_inv.reserve((size_t)n));
+            RL_HIP(hipMemcpy(s->rn_isq, isq.data(), isq.size() * sizeof(double), hipMemcpyHostToDevice));
+            RL_HIP(hipMemcpy(s->rn_sq, sq.data(), sq.size() * sizeof(double), hipMemcpyHostToDevice));
+            RL_HIP(hipMemcpy(s->rn_inv, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice));
+            if (s->rn_one == nullptr) {
+                const std::vector<double> one((size_t)n, 1.0);
+                RL_TRY(s->rn_one.upload(one));
+            }
+            s->rn_sumlog = sl;
+        }
+        s->rn_ver = s->noise_ver;
+    }
+    if (s->rn_why) { *why = s->rn_why; return RL_OK; }
+    if (s->rn_F_ver != s->noise_ver || s->rn_F_R != R || s->rn_F == nullptr) {
+        s->rn_F_R = 0;
+        RL_TRY(s->rn_F.reserve((size_t)R * n));
+        RL_LAUNCH(k_rn_table, dim3((n + 255) / 256, R), dim3(256), 0, st, (const double*)s->rp_F,
+                  (const double*)s->rn_isq, n, s->rn_F.get());
+#define RL_DZ_PROJ(R_) rp_project_plain<R_>(s, s->rn_F, R_, st, s->rn_F)
+        RL_DZ_RANKS(RL_DZ_PROJ);
+#undef RL_DZ_PROJ
+        RL_HIP(hipGetLastError());
+        std::vector<double> part((size_t)s->rp_nruns * R * R);
+        RL_HIP(hipMemcpy(part.data(), s->rp_part, part.size() * sizeof(double), hipMemcpyDeviceToHost));
+        s->rn_U.assign((size_t)D * R * R, 0.0);
+        for (int d = 0; d < D; ++d)
+            for (int c = s->h_run_ptr[d]; c < s->h_run_ptr[d + 1]; ++c)
+                for (int e = 0; e < R * R; ++e)
+                    s->rn_U[(size_t)d * R * R + e] += part[(size_t)c * R * R + e];
+        s->rn_F_R = R;
+        s->rn_F_ver = s->noise_ver;
+    }
+    return RL_OK;
+}
+
+// out = post (.) (I + F~_q map F~_q^T) (pre (.) in): the unit-noise apply between two row
+// scalings (pre == nullptr: none in front).  pre = post = e^-1/2 with the solve map is K~^-1 (or
+// the preconditioner's inverse); post = e^1/2 with the square-root map is the sample factor.
+static int rn_apply(rl_ski* s, const double* in, double* out, int nvec, hipStream_t st, const double* map,
+                    const double* pre, const double* post) {
+    rl_gridop* g = s->g;
+    const int n = s->n, R = g->lr_r, D = g->D;
+    const int nblk = std::max(1, std::min(RL_DZ_NBLK, (n + 1023) / 1024));
+    const double* x = in;
+    if (pre != nullptr) {
+        RL_TRY(s->rn_tmp.reserve((size_t)nvec * n));
+        RL_LAUNCH(k_dz_scale, dim3(nblk, nvec), dim3(256), 0, st, in, pre, n, s->rn_tmp.get());
+        x = s->rn_tmp;
+    }
+#define RL_DZ_PROJ(R_) rp_project_plain<R_>(s, x, nvec, st, s->rn_F)
+    RL_DZ_RANKS(RL_DZ_PROJ);
+#undef RL_DZ_PROJ
+    RL_LAUNCH(k_dz_mix, dim3((nvec + RL_DZ_VB - 1) / RL_DZ_VB), dim3(256),
+              (size_t)RL_DZ_VB * D * R * sizeof(double), st, (const double*)s->rp_part,
+              (const int*)s->rp_run_ptr, nvec, D, R, map, g->lr_zhat);
+#define RL_DZ_EXP(R_) rp_expand_plain<R_>(s, g->lr_zhat, out, nvec, s->rn_one, x, st, s->rn_F)
+    RL_DZ_RANKS(RL_DZ_EXP);
+#undef RL_DZ_EXP
+    RL_LAUNCH(k_rn_scale, dim3(nblk, nvec), dim3(256), 0, st, out, post, n);
+    RL_HIP(hipGetLastError());
+    return RL_OK;
+}
+
 // builds (or rebuilds, after a parameter / noise update) the factorisation; *ok = false with
 // a reason when the operator has no such form or the factorisation breaks down
 static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
@@ -1714,6 +1799,10 @@ static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
     // 360, ~0.1 s at 768): past D r = 576 a SMALL system's Krylov solve is cheaper than its
     // factorisation (a round of a 10^4-row system is 20 us), so such operators keep the Krylov path
     s->dz_hz = false;
+    s->dz_rows = false;
+    // (the 96-function preconditioner keeps a noise level per output: a handle with per-observation
+    // noise falls back to the 48 functions)
+    const bool hzw = hz_wanted(s) && !s->row_noise;
     if (Dr > 576 && (double)n < 1e5 * ((double)Dr / 576.0) * ((double)Dr / 576.0) * ((double)Dr / 576.0)) {
         s->dz_valid = false;
         *ok = false;
@@ -1739,7 +1828,7 @@ static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
             if (!(cap[q] >= 0.8))
                 cap_why = "not every top row is in the polynomial form, and the subspace holds less than 0.8 of a row's spectrum (no preconditioner either)";
         // (... which the 96-function basis below may still hold)
-        if (cap_why != nullptr && !hz_wanted(s)) { *why = cap_why; return RL_OK; }
+        if (cap_why != nullptr && !hzw) { *why = cap_why; return RL_OK; }
         hC = hCx.data();
     } else if ((int)g->lr_hC.size() < Q * R * R) {
         *why = "no host copy of the coefficient maps";
@@ -1747,9 +1836,16 @@ static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
     }
     RL_TRY(rp_prepare(s, std::max(R, 1)));
     if (s->rp_F == nullptr || s->rp_R != R) { *why = "no table of F"; return RL_OK; }
-    // per-output noise, rows per output, 1 / eps per row on the device: per NOISE update (a
+    // per-observation noise: the unit-noise problem of the scaled table (rl_rownoise.h) ...
+    const std::vector<double> unit((size_t)D, 1.0);
+    if (s->row_noise) {
+        const char* rn_why = nullptr;
+        RL_TRY(rn_ensure(s, R, st, &rn_why));
+        if (rn_why) { *why = rn_why; return RL_OK; }
+    }
+    // ... else per-output noise, rows per output, 1 / eps per row on the device: per NOISE update (a
     // parameter update alone does not walk the n rows again)
-    if (s->dz_eps_ver != s->noise_ver || (int)s->dz_eps.size() != D) {
+    else if (s->dz_eps_ver != s->noise_ver || (int)s->dz_eps.size() != D) {
         s->dz_eps.assign(D, 0.0);
         s->dz_eps_why = nullptr;
         for (int d = 0, a = 0; d < D && !s->dz_eps_why; ++d) {
@@ -1773,8 +1869,8 @@ static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
         }
         s->dz_eps_ver = s->noise_ver;
     }
-    if (s->dz_eps_why) { *why = s->dz_eps_why; return RL_OK; }
-    const std::vector<double>& eps = s->dz_eps;
+    if (!s->row_noise && s->dz_eps_why) { *why = s->dz_eps_why; return RL_OK; }
+    const std::vector<double>& eps = s->row_noise ? unit : s->dz_eps;
     std::vector<int> rows(D, 0);
     for (int d = 0, a = 0; d < D; ++d) {
         rows[d] = s->h_out_end[d] - a;
@@ -1782,7 +1878,7 @@ static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
     }
     // an operator without a polynomial row, of enough rows: the 96-function preconditioner (hz_*
     // above); whatever it declines falls back to the 48 functions
-    if (!exact && hz_wanted(s)) {
+    if (!exact && hzw) {
         bool hz_ok = false;
         const char* hz_why = "";
         RL_TRY(hz_try(s, eps, rows, &hz_ok, &hz_why));
@@ -1800,7 +1896,7 @@ static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
     }
     // Gram matrices of F on the unnormalised basis, once per (handle, rank): the columns of F
     // ARE a batch of R vectors (degree-major table)
-    if (s->dz_U_R != R) {
+    if (!s->row_noise && s->dz_U_R != R) {
 #define RL_DZ_PROJ(R_) rp_project_plain<R_>(s, s->rp_F, R_, st)
         RL_DZ_RANKS(RL_DZ_PROJ);
 #undef RL_DZ_PROJ
@@ -1818,7 +1914,7 @@ static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
     std::vector<double> Zs;
     double logdet = 0.0, pmin = 1.0, pmax = 1.0;
     std::vector<double> Zh;
-    if (!dz_host_map(D, R, Q, s->dz_U.data(), g->lr_hnu.data(), eps, rows, g->lr_hB.data(), hC, Zs, &logdet,
+    if (!dz_host_map(D, R, Q, s->row_noise ? s->rn_U.data() : s->dz_U.data(), g->lr_hnu.data(), eps, rows, g->lr_hB.data(), hC, Zs, &logdet,
                      &pmin, &pmax, why, s->dz_want_sample ? &Zh : nullptr))
         return RL_OK;
     RL_TRY(dz_upload_sample_map(s, Zh));
@@ -1826,12 +1922,14 @@ static int dz_ensure_poly(rl_ski* s, bool* ok, const char** why) {
         if (!std::isfinite(v)) { *why = "the solve map is not finite"; return RL_OK; }
     RL_TRY(s->dz_Zt.reserve(Zs.size()));
     RL_HIP(hipMemcpy(s->dz_Zt, Zs.data(), Zs.size() * sizeof(double), hipMemcpyHostToDevice));
-    s->dz_logdet = logdet;
+    // (unit noise: the map's log det is log det (I + L^T M L); the rows' own log e_i on top)
+    s->dz_logdet = s->row_noise ? s->rn_sumlog + logdet : logdet;
     s->dz_cond = (pmax / pmin) * (pmax / pmin);
     s->dz_param_ver = g->param_ver;
     s->dz_noise_ver = s->noise_ver;
     s->dz_R = R;
     s->dz_exact = exact;
+    s->dz_rows = s->row_noise;
     s->dz_valid = true;
     *ok = true;
     return RL_OK;
@@ -1862,6 +1960,11 @@ static int dz_apply(rl_ski* s, const double* in, double* out, int nvec, hipStrea
     rl_gridop* g = s->g;
     if (s->pc.active) return pc_apply(s, in, out, nvec, st, s->pc.Mt, s->pc.inv, s->pc.inv, s->pc.inv);
     if (s->dz_hz) return hz_apply(s, in, out, nvec, st, map, diag);
+    if (s->dz_rows) {
+        if (map != nullptr || diag != nullptr)
+            return fail(RL_ELIMIT, "dz_apply: no other map or diagonal on a handle with per-observation noise");
+        return rn_apply(s, in, out, nvec, st, s->dz_Zt, s->rn_isq, s->rn_isq);
+    }
     if (map == nullptr) map = s->dz_Zt;
     if (diag == nullptr) diag = s->dz_inv;
     const int R = g->lr_r, D = g->D;
@@ -2334,6 +2437,24 @@ extern "C" int rl_ski_precond_sample(rl_ski* s, const double* Win, double* Rout,
     if (logdet_p) *logdet_p = s->dz_logdet;
     if (nvec == 0) return RL_OK;
     const int n = s->n;
+    if (s->dz_rows) {
+        // per-observation noise: S = E^1/2 (I + F~_q Zh F~_q^T), the unit-noise square-root factor
+        // behind one row scaling (S S^T = P)
+        RL_TRY(rp_prepare(s, std::max(nvec, g->lr_r)));
+        RL_TRY(ski_reserve_perm(s, nvec));
+        RL_TRY(lr_reserve(g, nvec));
+        const double* Wi = Win;
+        double* Ri = Rout;
+        if (s->permuted) {
+            permute_rows(s, Win, s->P1, nvec, 0, st);
+            Wi = s->P1;
+            Ri = s->P2;
+        }
+        RL_TRY(rn_apply(s, Wi, Ri, nvec, st, s->dz_Zh, nullptr, s->rn_sq));
+        if (s->permuted) permute_rows(s, Ri, Rout, nvec, 1, st);
+        RL_HIP(hipGetLastError());
+        return RL_OK;
+    }
     if (s->dz_isq_ver != s->noise_ver || s->dz_isq == nullptr) {
         std::vector<double> isq((size_t)n);
         for (int i = 0; i < n; ++i) isq[i] = 1.0 / std::sqrt(s->h_noise[i]);
@@ -2381,17 +2502,25 @@ extern "C" int rl_ski_inverse_diag(rl_ski* s, double* out, int* exact, void* str
     if (s->dz_hz)
         return fail(RL_ELIMIT, "rl_ski_inverse_diag: the factorisation is on the 96-function basis, whose map is "
                                "kept in blocks of 48 functions: no diagonal from it");
-    if (s->rp_F == nullptr || s->rp_R != g->lr_r || s->dz_R != g->lr_r || s->dz_Zt == nullptr || s->dz_inv == nullptr)
+    if (s->rp_F == nullptr || s->rp_R != g->lr_r || s->dz_R != g->lr_r || s->dz_Zt == nullptr ||
+        (s->dz_rows ? s->rn_F == nullptr || s->rn_F_R != g->lr_r : s->dz_inv == nullptr))
         return fail(RL_ELIMIT, "rl_ski_inverse_diag: the table of F does not match the factorisation");
     RL_HIP(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)stream;
     (void)st;                              // (the emulator's launch takes no stream)
     const int* perm = s->permuted ? (const int*)s->perm : (const int*)nullptr;
 #define RL_DZ_DIAG(R_)                                                                             \
-    RL_LAUNCH((k_dz_diag<R_>), dim3((s->n + 255) / 256), dim3(256), 0, st, (const double*)s->rp_F, s->n, \
-              g->D, (const int*)s->rp_out_end, (const double*)s->dz_Zt, (const double*)s->dz_inv, perm, out)
+    RL_LAUNCH((k_dz_diag<R_>), dim3((s->n + 255) / 256), dim3(256), 0, st, Ftab, s->n,                 \
+              g->D, (const int*)s->rp_out_end, (const double*)s->dz_Zt, dinv, perm, out)
+    // (per-observation noise: (1 + f~_i^T Zs[d, d] f~_i) / e_i -- the unit-noise diagonal on the
+    // scaled table, then the rows' 1 / e_i)
+    const double* Ftab = s->dz_rows ? (const double*)s->rn_F : (const double*)s->rp_F;
+    const double* dinv = s->dz_rows ? (const double*)s->rn_one : (const double*)s->dz_inv;
     RL_DZ_RANKS(RL_DZ_DIAG);
 #undef RL_DZ_DIAG
+    if (s->dz_rows)
+        RL_LAUNCH(k_rn_scale_rows, dim3((s->n + 255) / 256), dim3(256), 0, st, out, (const double*)s->rn_inv,
+                  perm, s->n);
     RL_HIP(hipGetLastError());
     *exact = s->dz_exact ? 1 : 0;
     return RL_OK;

@@ -291,9 +291,10 @@ class LMCOperator(SumMatrix):
     """K~ = sum over active-dimension sets of GridKernel + Diag(noise): the
     SumMatrix gen_grid_kernel returns (reference grid_kernel.py:66-74), with
     ONE device handle (all terms and the noise) that serves the fused product
-    and the batched solver."""
+    and the batched solver.  ``extra``: known per-observation variances (n values >= 0, the
+    rows' order) added to the noise diagonal, never a parameter (SkiOp.set_noise_rows)."""
 
-    def __init__(self, grid_kernels, noise_diag_matrix, noise, lens):
+    def __init__(self, grid_kernels, noise_diag_matrix, noise, lens, extra=None):
         grid_kernels = list(grid_kernels)
         super().__init__(grid_kernels + [noise_diag_matrix])
         self._gks = grid_kernels
@@ -303,9 +304,18 @@ class LMCOperator(SumMatrix):
         for gk in grid_kernels[1:]:
             W, WT = gk.ski.W, gk.ski.WT
             self.term_of[gk.active_dim] = self._skiop.add_term(gk._op, W, WT)
-        self._skiop.set_noise(noise, lens)
+        self.extra = None if extra is None else np.ascontiguousarray(as_f64(extra).reshape(-1))
+        self._set_noise(noise, lens)
         self.lens = list(lens)
         self._noise_version = 0
+
+    def _set_noise(self, noise, lens):
+        if self.extra is None:
+            self._skiop.set_noise(noise, lens)
+            self.Ks[-1].v = np.repeat(noise, lens)
+        else:
+            self._skiop.set_noise_rows(noise, lens, self.extra)
+            self.Ks[-1].v = np.repeat(noise, lens) + self.extra
 
     def state_version(self):
         """A value that changes with every GridKernel.update() of a term and every
@@ -347,17 +357,17 @@ class LMCOperator(SumMatrix):
             np.ascontiguousarray(X.T, dtype=np.float64)).T
 
     def update_noise(self, noise, lens):
-        self._skiop.set_noise(noise, lens)
-        self.Ks[-1].v = np.repeat(noise, lens)
+        self._set_noise(noise, lens)
         self._noise_version += 1
 
 
 def gen_grid_kernel(fk, grid_dists, interpolants, lens_per_output,
-                    device_index=0, reference_slfm_identity=False, precond_rank=0):
+                    device_index=0, reference_slfm_identity=False, precond_rank=0, fixed_noise=None):
     """(K~, {active_dim: GridKernel}) exactly as the reference returns them
     (grid_kernel.py:49-74): one GridKernel per active-dimension set, summed
     with the noise.  precond_rank > 0 opts in to the pivoted-Cholesky preconditioner of that
-    rank for operators without a polynomial factorisation (SkiOp.set_pivchol)."""
+    rank for operators without a polynomial factorisation (SkiOp.set_pivchol).  fixed_noise: known
+    per-observation variances (n values, the rows' order) on top of fk.noise (LMCOperator)."""
     grid_kerns = {}
     for active_dim in fk.active_dims:
         W, WT = interpolants[active_dim]
@@ -366,7 +376,7 @@ def gen_grid_kernel(fk, grid_dists, interpolants, lens_per_output,
             active_dim, device_index=device_index,
             reference_slfm_identity=reference_slfm_identity)
     noise = Diag(np.repeat(fk.noise, lens_per_output))
-    K = LMCOperator(list(grid_kerns.values()), noise, fk.noise, lens_per_output)
+    K = LMCOperator(list(grid_kerns.values()), noise, fk.noise, lens_per_output, extra=fixed_noise)
     if precond_rank:
         K.device_operator().set_pivchol(precond_rank)
     return K, grid_kerns

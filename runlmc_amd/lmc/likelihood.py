@@ -293,15 +293,21 @@ class ExactLMCLikelihood(LMCLikelihood):
         dL/dA_q = 1/2 A_q (S_q + S_q^T)         (dB = e_j a_i^T + a_i e_j^T)
         dL/dkappa_q = 1/2 diag(S_q)             (dB = e_i e_i^T)
         dL/dtheta_qp = 1/2 sum_ab B_q[a, b] S_qp[a, b]
-        dL/dnoise_d = 1/2 sum_{i in d} M_ii."""
+        dL/dnoise_d = 1/2 sum_{i in d} M_ii.
 
-    def __init__(self, functional_kernel, Xs, Ys, device_index=0):
+    fixed_noise: known per-observation variances (n values >= 0, the outputs concatenated) added to
+    K's diagonal next to the per-output noise (ExactOp.set_row_noise).  They are no parameter:
+    dK/dnoise_d stays the indicator diagonal of output d, so every gradient keeps its form."""
+
+    def __init__(self, functional_kernel, Xs, Ys, device_index=0, fixed_noise=None):
         super().__init__(functional_kernel, Ys)
         fk = functional_kernel
         X = self._stack(Xs, fk)
         if X.shape[0] != len(self.y):
             raise ValueError('Xs hold %d points, Ys %d' % (X.shape[0], len(self.y)))
         self._op = ExactOp(X.shape[0], X.shape[1], device_index=device_index)
+        if fixed_noise is not None:
+            self._op.set_row_noise(fixed_noise)
         self._op.set(X, self.lens, fk.kernels, fk.coreg_mats(), fk.noise)
         self._logdet = self._op.factor()
         self._alpha_dev = self._op.solve(torch.from_numpy(as_f64(self.y)).to(self._op.device))

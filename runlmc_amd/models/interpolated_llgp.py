@@ -24,6 +24,11 @@ Every product, solve and gradient inside runs on the device
   parameters go through paramz's Logexp (softplus) transform as in the
   reference (functional_kernel.py:130,185; rbf.py:33).
 * `max_procs` is accepted and ignored (no process pool).
+* ``fixed_noise``: known per-observation noise variances v_i (stated error bars, sigma^2 / count of
+  binned means, down-weighted points) on top of the learned per-output noise:
+  K~ = sum_t W_t K_t W_t^T + diag(eps_d(i) + v_i).  They are data, never a parameter.  ``predict``
+  and ``posterior_samples(noise=True)`` describe a NEW observation, whose error bar is not known:
+  they keep adding the per-output noise eps_d only.
 """
 import logging
 
@@ -67,17 +72,23 @@ class InterpolatedLLGP:
                  name='lmc', metrics=False, prediction='on-the-fly',
                  max_procs=None, trace_iterations=15, tolerance=1e-4,
                  functional_kernel=None, group=None, device_index=0, device_probes=None,
-                 variance_batch=None, precond_rank=0):
+                 variance_batch=None, precond_rank=0, fixed_noise=None):
         self.name = name
         self.input_dim, self.output_dim = self._validate_io(Xs, Ys)
         self.normalizer = None
         Ys = [np.asarray(Y, dtype=float) for Y in Ys]
+        # fixed_noise: one array per output, as long as that output's Y, in the units of Y^2
+        fixed = self._validate_fixed_noise(fixed_noise, Ys)
         if normalize:
             self.normalizer = [(Y.mean(), Y.std()) for Y in Ys]
             if any(s == 0 for _, s in self.normalizer):
                 raise ValueError('an output has no variance')
             Ys = [(Y - mu) / sd for Y, (mu, sd) in zip(Ys, self.normalizer)]
+            if fixed is not None:
+                fixed = [v / sd ** 2 for v, (_, sd) in zip(fixed, self.normalizer)]
         self.Ys = Ys
+        # (the rows' order, the units of the normalised Ys; None: every path as without it)
+        self.fixed_noise = None if fixed is None else np.concatenate(fixed)
         self.Xs = [np.asarray(X, dtype=float).reshape(len(X), -1) for X in Xs]
         if not functional_kernel:
             raise ValueError('functional_kernel must be provided')
@@ -159,6 +170,26 @@ class InterpolatedLLGP:
         if len(dims) != 1:
             raise ValueError('inputs differ in dimension')
         return dims.pop(), len(Ys)
+
+    @staticmethod
+    def _validate_fixed_noise(fixed_noise, Ys):
+        if fixed_noise is None:
+            return None
+        if len(fixed_noise) != len(Ys):
+            raise ValueError('fixed_noise must have one array per output (%d), got %d'
+                             % (len(Ys), len(fixed_noise)))
+        out = []
+        for d, (v, Y) in enumerate(zip(fixed_noise, Ys)):
+            v = np.asarray(v, dtype=float).reshape(-1)
+            if len(v) != len(Y):
+                raise ValueError('fixed_noise[%d] has %d values, output %d has %d observations'
+                                 % (d, len(v), d, len(Y)))
+            if not np.all(np.isfinite(v)):
+                raise ValueError('fixed_noise[%d] holds values that are not finite' % d)
+            if np.any(v < 0):
+                raise ValueError('fixed_noise[%d] holds negative variances' % d)
+            out.append(v)
+        return out
 
     @staticmethod
     def _wrap(v, active_dims):
@@ -257,7 +288,8 @@ class InterpolatedLLGP:
         if self._K is None:
             self._K, self._grid_kernels = gen_grid_kernel(
                 fk, self.lags, self.interpolants, lens,
-                device_index=self._device_index, precond_rank=self.precond_rank)
+                device_index=self._device_index, precond_rank=self.precond_rank,
+                fixed_noise=self.fixed_noise)
         else:
             # same grid and interpolants: only spectra, factors and noise change
             for ad, gk in self._grid_kernels.items():
@@ -303,7 +335,8 @@ class InterpolatedLLGP:
         parameters_changed (reference interpolated_llgp.py:247-250)."""
         if 'dense' not in self._caches:
             self._caches['dense'] = ExactLMCLikelihood(
-                self._functional_kernel, self.Xs, self.Ys, device_index=self._device_index)
+                self._functional_kernel, self.Xs, self.Ys, device_index=self._device_index,
+                fixed_noise=self.fixed_noise)
         return self._caches['dense']
 
     def K(self):
@@ -397,6 +430,8 @@ class InterpolatedLLGP:
             fk = self._functional_kernel
             X = np.vstack(self.Xs)
             op = ExactOp(X.shape[0], X.shape[1], device_index=self._device_index)
+            if self.fixed_noise is not None:
+                op.set_row_noise(self.fixed_noise)
             op.set(X, [len(x) for x in self.Xs], fk.kernels, fk.coreg_mats(), fk.noise)
             self._caches['light_exact'] = op
         return self._caches['light_exact']
@@ -612,7 +647,8 @@ class InterpolatedLLGP:
 
         The held-out quantity is the noisy observation, so the noise is part of the variance:
         ``variances[d] - noise_d * sd_d ** 2`` is the latent function's (sd_d = 1 without
-        normalisation).
+        normalisation); with ``fixed_noise`` the held-out row's own variance is part of it too, and
+        ``variances[d] - noise_d * sd_d ** 2 - fixed_noise[d]`` is the latent function's.
 
         method and **kw (probes, n_probes, seed, batch, tol, control_variate) go to
         ``approx.loo.inverse_diagonal``: 'direct' (no solve at all, operators whose factorisation
